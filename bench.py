@@ -23,14 +23,20 @@ Other BASELINE.json configurations are one command each:
 `python -m torch.distributed.run --nproc-per-node N`; the world size must equal --gpus, and with the RCCL backend N GPUs
 must be visible -- anything else stops with an error instead of reporting a smaller job.
 
+A plain run sets up, warms up, times the --steps frames and prints the result line: the headline (`value` frames/s,
+`ms_per_step`, `dtype`, the per-frame spread) and nothing that needs launches of its own.  --full adds everything else
+that is measured outside the timed region (the records listed below); --dump-outputs DIR writes the image of the last
+timed frame as DIR/image.npy (float32 [1, 3, H, W]; rank r > 0: image_rank<r>.npy) for comparing two builds output for
+output -- the scene, weights and style are seeded, so the inputs are the same in every run with the same arguments.
+
 Output: stdout carries exactly ONE line, the last one, <= 6 KB of JSON (scenedreamer_amd/benchline.py: `compact`): the driver
-contract's keys, numeric `roofline` (dominant kernel: the field MLP) / `roofline_grid_sampler` / `roofline_cnn` /
-`roofline_rvip` / `roofline_sky`, at N=1 `cpu_baseline` (the unmodified reference on this box's host cores) and `precision`,
-and one number each for the unmodified reference loop on the fast shims, configs 3 / 5 on this GPU, the fp32 rung, the
-no-skip floor (fog weights), colour skipping off, and the per-style one-off costs.  The FULL record (gates, per-tile
-errors, per-launch tables, the prose that explains each figure) is written to `bench_detail.json` next to this file (or
-$SDN_BENCH_DETAIL).  Everything else that would reach stdout (library chatter, the reference loop's own prints) is sent to
-stderr at file-descriptor level.  --only dropin|other prints just that record.
+contract's keys and, with --full, numeric `roofline` (dominant kernel: the field MLP) / `roofline_grid_sampler` /
+`roofline_cnn` / `roofline_rvip` / `roofline_sky`, at N=1 `cpu_baseline` (the unmodified reference on the host cores) and
+`precision`, and one number each for the unmodified reference loop on the fast shims, configs 3 / 5 on this GPU, the fp32
+rung, the no-skip floor (fog weights), colour skipping off, and the per-style one-off costs.  The FULL record (gates,
+per-tile errors, per-launch tables, the prose that explains each figure) is written to `bench_detail.json` next to this file
+(or $SDN_BENCH_DETAIL).  Everything else that would reach stdout (library chatter, the reference loop's own prints) is sent
+to stderr at file-descriptor level.  --only dropin|other prints just that record.
 """
 import argparse
 import json
@@ -62,8 +68,14 @@ BYTES_PER_SAMPLE_FUSED = 16404    # 16384 gather + 20 coords in
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed frames per rank (default 10; --config 4: 256 / N, --config 5: 6)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every record measured outside the timed region (roofline / per-kernel timing, other apron, "
+                         "delivered rate, CPU baseline and precision, floor / style-cost records, other configs, drop-in loop)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the image of the last timed frame to DIR/image.npy (float32)")
     ap.add_argument("--mode", default=os.environ.get("SDN_BENCH_MODE", "auto"), choices=["auto", "fused", "unfused", "dropin"],
                     help="fused / unfused: which per-pixel path this package's frame loop uses; dropin = --only dropin (the UNMODIFIED "
                          "reference generator's inference_givenstyle loop on install_shims(fast=True))")
@@ -109,19 +121,42 @@ def parse():
     args = ap.parse_args()
     if args.mode == "dropin":
         args.mode, args.only = "auto", "dropin"
-    if args.profile:
+    if args.profile:     # the roofline record of the traced launches is what a --profile run is for
+        args.full = True
         args.no_extras = args.no_cpu_baseline = args.no_dropin = args.no_other_configs = True
         os.environ.setdefault("SDN_FIELD_GATE", "0")    # no calibration launches in the trace (scenedreamer_amd.renderer.FIELD_GATE)
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = args.no_dropin = args.no_other_configs = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.config == 3:
         args.height, args.width, args.samples, args.no_extras = 1080, 1920, 40, True
     elif args.config == 4:     # the whole 256-pose orbit, sharded: K = 256 / N frames per rank
         args.cam_maxstep, args.pose_stride = 256, 1
-        args.steps = max(1, 256 // world)
+        if args.steps is None:
+            args.steps = max(1, 256 // world)
     elif args.config == 5:
         args.height, args.width, args.samples, args.bench_mode, args.no_extras = 2160, 3840, 40, "tile-parallel", True
-        args.steps = min(args.steps, 6)
+        if args.steps is None:
+            args.steps = 6
+    if args.steps is None:
+        args.steps = 10
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
+
+
+def dump_outputs(dirname, arrays, limit):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  One larger than `limit` bytes is thinned to every s-th row
+    and column (the smallest s that fits: the same sample in every run) and saved as <name>_stride<s>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        s = 1
+        while a[..., ::s, ::s].nbytes > limit:
+            s += 1
+        if s > 1:
+            a, name = np.ascontiguousarray(a[..., ::s, ::s]), f"{name}_stride{s}"
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline(args, weights, scene, z, genc):
@@ -790,9 +825,11 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         sdist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and img is not None:       # (tile-parallel: only rank 0 receives the stitched image)
+        dump_outputs(args.dump_outputs, {"image" if rank == 0 else f"image_rank{rank}": img}, (64 << 20) // world)
 
     tp_stats = None
-    if tile_parallel:       # one more frame, outside the timed region, with per-rank device timing of the bands
+    if tile_parallel and args.full:       # one more frame, outside the timed region, with per-rank device timing of the bands
         tp_stats = {}
         sdist.render_frame_tile_parallel(R, frame_pose(args.warmup), hw, args.samples, mode=mode, balance="feedback", stats=tp_stats)
         barrier()
@@ -804,7 +841,7 @@ def main():
     if tile_parallel:
         args.no_extras = True
     n_del = 0 if args.no_extras else min(args.steps, 10)
-    pinned = [torch.empty((hw[0], hw[1], 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+    pinned = [torch.empty((hw[0], hw[1], 3), dtype=torch.uint8).pin_memory() for _ in range(2 if n_del else 0)]
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     if n_del and pipelined:     # the path that is timed above (render_frames), every frame converted and copied to pinned host memory
@@ -819,7 +856,7 @@ def main():
 
     # ---- per-stage breakdown + roofline of the dominant kernel (outside the timed region) ----------
     stages = {}
-    for k in range(0 if tile_parallel else min(args.steps, 5)):
+    for k in range(0 if tile_parallel or not args.full else min(args.steps, 5)):
         R.render_frame(frame_pose(args.warmup + k), hw, args.samples, mode=mode, timers=stages, apron=args.apron)
     stage_ms = {k: float(np.mean(v)) for k, v in stages.items()}
     # the same frames with the other apron setting (outside the timed region; reported for transparency)
@@ -834,7 +871,7 @@ def main():
     torch.cuda.synchronize()
     other_ms = 1000.0 * (time.perf_counter() - t1) / n_other if n_other else None
     roof_cnn = roof_sky = None
-    if tile_parallel:     # per-kernel records on this rank's band (every rank does 1/N of the frame)
+    if tile_parallel or not args.full:     # (tile-parallel: no per-kernel records on this rank's band, 1/N of the frame)
         roof, roof_grid = None, None
     elif probe.get("mlp_kernel"):
         # the launches of the timed region itself: average duration from HIP events recorded around every launch on the
@@ -921,7 +958,7 @@ def main():
     else:
         roof, roof_grid = R.measure_roofline(frame_pose(args.warmup), hw, args.samples, mode)
     roof_rvip = None
-    if rank == 0 and not tile_parallel:
+    if rank == 0 and not tile_parallel and args.full:
         roof_rvip = rvip_roofline(R, timed_poses, hw)
         if roof is not None and roof.get("bound") == "mfma" and not args.profile:
             sustained_ceiling(roof)
@@ -947,6 +984,8 @@ def main():
         except Exception as ex:  # noqa: BLE001
             style_cost = {"error": f"{type(ex).__name__}: {ex}"}
 
+    # config 4 is the whole orbit split over the ranks (K = 256 / N each); an explicit --steps other than that K times part of it
+    partial_orbit = args.config == 4 and args.steps != max(1, maxstep // world)
     if rank == 0:
         fps = (1 if tile_parallel else world) * args.steps / elapsed
         out = {
@@ -956,13 +995,14 @@ def main():
             "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True,
             # config 5: one frame split over the ranks; config 4: the 256 frames of the orbit split over the ranks (K = 256 / N per rank):
             # both fixed total work = strong.  Default (and what the driver's SCALE run is): every rank renders K frames = weak.
-            "scaling": "strong" if (tile_parallel or args.config == 4) else "weak",
+            "scaling": "strong" if (tile_parallel or (args.config == 4 and not partial_orbit)) else "weak",
             "vs_baseline": None, "dtype": R.compute_dtype(mode), "data": "synthetic",
             "config": {"workload": f"{args.width}x{args.height}, num_samples={args.samples}, "
                                    f"scene_size={args.scene_size}, cam pattern 0 (pose stride {args.pose_stride} of {maxstep} poses), "
                                    + ("1 frame per step, row bands over the ranks (tile-parallel)" if tile_parallel
-                                      else "1 frame per rank per step"),
-                       "baseline_config": args.config or (2 if (hw, args.samples, args.scene_size) == ((540, 960), 24, 2048) else None),
+                                      else "1 frame per rank per step")
+                                   + (f", {args.steps * world} of the {maxstep} orbit frames" if partial_orbit else ""),
+                       "baseline_config": None if partial_orbit else args.config or (2 if (hw, args.samples, args.scene_size) == ((540, 960), 24, 2048) else None),
                        "path": mode, "apron": ("minimal" if mode == "fused" else "reference") if tile_parallel else args.apron,
                        "bands": ({"rows": tp_stats.get("bands"), "band_ms": tp_stats.get("band_ms"), "imbalance_max_over_mean": tp_stats.get("imbalance"),
                                   "cut": "equal estimated work (dist.balanced_row_bands on a 1/16-resolution ray cast)" if world > 1 else "one band",

@@ -251,7 +251,7 @@ def test_bench_py_multi_rank_path_two_ranks_on_one_gpu(bench_mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--scene-size", "256", "--height", "96", "--width", "136", "--samples", "12", "--no-extras",
-           "--bench-mode", bench_mode]
+           "--bench-mode", bench_mode, "--full"]
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         detail_path = os.path.join(tmp, "detail.json")
@@ -286,7 +286,7 @@ def test_bench_py_single_gpu_stdout_is_one_small_json_line():
     with tempfile.TemporaryDirectory() as tmp:
         detail_path = os.path.join(tmp, "detail.json")
         cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--scene-size", "256",
-               "--height", "96", "--width", "136", "--samples", "12", "--dropin-frames", "3", "--cpu-budget-s", "5"]
+               "--height", "96", "--width", "136", "--samples", "12", "--dropin-frames", "3", "--cpu-budget-s", "5", "--full"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root,
                            env=dict(os.environ, SDN_BENCH_DETAIL=detail_path, SDN_CPU_THREADS="16"))
         assert r.returncode == 0, r.stderr[-3000:]
@@ -307,3 +307,64 @@ def test_bench_py_single_gpu_stdout_is_one_small_json_line():
     # the detail file is the full record: everything on the line is in it, plus what the line leaves out
     assert full["value"] == pytest.approx(d["value"], rel=1e-4) and "gates" in full["precision"] and "timing" in full["roofline"]
     assert (full["floor"]["passes_skipped_by_termination"], full["floor"]["colour_branch_skipped_fraction"]) == (0.0, 0.0)
+
+
+def test_bench_py_plain_run_times_steps_and_dumps_the_last_frame():
+    """A plain run (no --full) is the headline alone: --steps timed frames, the result line's head keys, none of the records
+    that --full measures outside the timed region.  --dump-outputs writes the LAST timed frame: the image of orbit frame
+    warmup + steps - 1 as bench.py's loop renders it in this process, for two different --steps.  A config-4 run with an
+    explicit --steps that does not cover the orbit is not labelled as config 4."""
+    import json
+    import subprocess
+    import sys
+    import tempfile
+    from scenedreamer_amd import camera, synth
+    from scenedreamer_amd import scene as scene_mod
+    from scenedreamer_amd.renderer import Renderer
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hw, ns, warmup = (96, 136), 12, 1
+    small = ["--scene-size", "256", "--height", str(hw[0]), "--width", str(hw[1]), "--samples", str(ns)]
+
+    def bench(tmp, *args):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *small, *args]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root,
+                           env=dict(os.environ, SDN_BENCH_DETAIL=os.path.join(tmp, "detail.json")))
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert r.stdout.count("\n") == 1, r.stdout[-1500:]
+        return json.loads(r.stdout)
+
+    dumped, lines = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for steps in (3, 4):
+            out = os.path.join(tmp, f"out{steps}")
+            lines[steps] = bench(tmp, "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", out)
+            assert os.listdir(out) == ["image.npy"]
+            dumped[steps] = np.load(os.path.join(out, "image.npy"))
+        c4 = bench(tmp, "--config", "4", "--steps", "2", "--warmup", "1")
+        c4_workload = json.load(open(os.path.join(tmp, "detail.json")))["config"]["workload"]     # (the line cuts it to 120 characters)
+    for steps, d in lines.items():
+        assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"]
+        assert len(d["frame_ms_p10_p50_p90"]) == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["roofline"] is None and not d.get("stage_ms")
+        assert not {"cpu_baseline", "roofline_rvip", "roofline_cnn", "floor_frames_per_s", "dropin_frames_per_s"} & set(d)
+    assert c4["steps"] == 2 and c4["scaling"] == "weak" and "baseline_config" not in c4["config"]
+    assert c4_workload.endswith(", 2 of the 256 orbit frames"), c4_workload
+
+    # bench.py's renderer and loop for the same arguments: compact volume, seeded weights / style, frame k = orbit pose 2k of 40,
+    # the warm-up frames and then the timed trajectory through render_frames (a fresh renderer per run, as each run is a process)
+    dev = torch.device("cuda", 0)
+    scene = scene_mod.to_compact(synth.make_scene(256, 3407, device=dev))
+    weights = synth.make_weights(0)
+    poses = camera.eval_camera_poses(scene, maxstep=40)
+    pose = lambda k: poses[(2 * k) % 40]
+    for steps, img in dumped.items():
+        R = Renderer(weights, scene, dev)
+        R.set_style(synth.make_style(8888))
+        for _ in R.render_frames([pose(k) for k in range(warmup)], hw, ns, mode="fused", apron="minimal"):
+            pass
+        frames = [im.clone() for im in R.render_frames([pose(warmup + k) for k in range(steps)], hw, ns, mode="fused", apron="minimal")]
+        last, before = frames[-1].cpu().numpy(), frames[-2].cpu().numpy()
+        assert img.dtype == np.float32 and img.shape == (1, 3) + hw and np.isfinite(img).all()
+        err_last, err_before = float(np.abs(img - last).max()), float(np.abs(img - before).max())
+        print(f"--steps {steps}: dump vs last timed frame {err_last:.2e}, vs the frame before it {err_before:.2e}")
+        assert err_last < 1e-4 < err_before

@@ -685,3 +685,28 @@ def test_busiest_window_equals_pooling():
         box = F.avg_pool2d(g[None, None].double(), (Hc, Wc), stride=8)[0, 0]
         k = int(box.argmax())
         assert _busiest_window(g, Hc, Wc) == ((k // box.shape[1]) * 8, (k % box.shape[1]) * 8)
+
+
+def test_bench_py_steps_sets_the_timed_steps_and_full_gates_the_extra_records(monkeypatch):
+    """bench.py's arguments: an explicit --steps is the number of timed steps (--config 4 / 5 only supply its default); a plain
+    run turns off every record measured outside the timed region, --full (and --profile) keeps them."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_args", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "3")
+    assert (a.steps, a.warmup, a.full) == (7, 3, False) and a.no_extras and a.no_cpu_baseline and a.no_dropin and a.no_other_configs
+    a = parse("--full")
+    assert a.steps == 10 and a.full and not (a.no_extras or a.no_cpu_baseline or a.no_dropin or a.no_other_configs)
+    assert parse("--profile").full
+    assert parse("--config", "4").steps == 256 and parse("--config", "4", "--steps", "5").steps == 5
+    assert parse("--config", "5").steps == 6 and parse("--config", "5", "--steps", "20").steps == 20
+    with pytest.raises(SystemExit):
+        parse("--steps", "0")
