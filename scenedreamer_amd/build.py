@@ -18,17 +18,23 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsdnative.so")
 ARCH = "gfx950"
 
+ABLATION = ["-DSDN_MLP_ABLATION"] if os.environ.get("SDN_MLP_ABLATION") else []
+# the translation units on the MLP layer machinery (csrc/mlp_layers.h).  No SLP vectorisation: hipcc pairs fp32 ops into v_pk_*
+# and pays for it with v_mov shuffles and spills in the MLP kernel
+# (SDN_FIELD_CFLAGS: extra -D switches for timing ablations, tools/ab_libs.sh -- never set for a product build)
+MLP_FLAGS = ["-fno-slp-vectorize"] + ABLATION + os.environ.get("SDN_FIELD_CFLAGS", "").split()
+
 # file -> extra flags
 SOURCES = {
     "capi.hip": [],
     "rvip.hip": ["-ffp-contract=off"],  # bit-exact vs the oracle: no FMA contraction
     "posenc.hip": [],
     "gridenc.hip": [],
-    # no SLP vectorisation: hipcc pairs fp32 ops into v_pk_* and pays for it with v_mov shuffles and spills in the MLP kernel
-    # (SDN_FIELD_CFLAGS: extra -D switches for timing ablations, tools/ab_libs.sh -- never set for a product build)
-    "field.hip": ["-fno-slp-vectorize"] + (["-DSDN_MLP_ABLATION"] if os.environ.get("SDN_MLP_ABLATION") else [])
-                 + os.environ.get("SDN_FIELD_CFLAGS", "").split(),
-    "cnn.hip": (["-DSDN_MLP_ABLATION"] if os.environ.get("SDN_MLP_ABLATION") else []),
+    "field.hip": MLP_FLAGS,
+    "sky.hip": MLP_FLAGS,
+    "cnn_ends.hip": MLP_FLAGS,
+    "mlp_pack.hip": MLP_FLAGS,
+    "cnn.hip": ABLATION,
     "scene.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

@@ -1,8 +1,8 @@
 """Host side of the MFMA render CNN (csrc/cnn.hip): RenderCNN.forward + tanh
-(imaginaire/generators/gancraft_base.py:202-225, :588-603).  Six launches: the head (`sdn_conv_head`, csrc/field.hip: net_out
+(imaginaire/generators/gancraft_base.py:202-225, :588-603).  Six launches: the head (`sdn_conv_head`, csrc/cnn_ends.hip: net_out
 rows -> conv1 -> LeakyReLU -> y planes in one kernel; `chain = False`: sdn_conv_planes_from_f32 + conv1 as a conv_kernel launch),
 conv2a/2b/3a/3b (3x3), then the tail conv4a -> conv4b (+ residual) -> conv4 -> tanh as ONE register-resident chain on the
-field MLP's layer machinery (`sdn_conv_chain`, csrc/field.hip: the 256-channel activation is read once and never written;
+field MLP's layer machinery (`sdn_conv_chain`, csrc/cnn_ends.hip: the 256-channel activation is read once and never written;
 `chain = False`: conv4a / conv4b as conv_kernel launches with conv4 + tanh folded into conv4b's epilogue); activations
 travel as f16 hi/lo planes.
 

@@ -1,7 +1,8 @@
 // The render CNN's convolutions on MFMA for gfx950 (RenderCNN, imaginaire/generators/gancraft_base.py:175-225): the 3x3
 // 256 -> 256 ones (conv2a/2b/3a/3b) and, with TAPS = 1, the 1x1 ones (conv1 64 -> 256, conv4a/4b 256 -> 256; conv4
 // 256 -> 3 + tanh is folded into conv4b's epilogue), with the same 3-term f16 split / f32 accumulate arithmetic
-// as the field MLP (field.hip): the image must stay within 1e-3 of the fp32 reference, which plain f16 does not.
+// as the field MLP (mlp_layers.h): the image must stay within 1e-3 of the fp32 reference, which plain f16 does not.
+// (By default the 1x1 ends run on the field MLP's layer machinery instead: head_kernel and chain_kernel, cnn_ends.hip.)
 //
 // Formulation (transposed implicit GEMM): D^T[cout][pixel] = sum_{tap, cin} W[cout][cin][tap] * X[cin][pixel + tap].
 //   * MFMA columns = 32 pixels (an 8 x 4 patch) per wave, 8 waves (a 16 x 16 patch, 2 waves per SIMD) per workgroup;
@@ -15,7 +16,7 @@
 //     256-B runs.  (With channels-last [pixel][256] every 16-B piece sat in its own 128-B line: 8x L2->L1 read
 //     amplification, the first version of this kernel was bound by that, not by the matrix pipe.)
 //   * 5-slot LDS ring (32 KiB per slot = the whole 160 KiB LDS), 4 k-steps ahead, counted vmcnt + raw s_barrier per k-step exactly as
-//     in field.hip; because every vector-memory operation in the main loop is a DMA with the same look-ahead, no
+//     in the field MLP's weight ring (mlp_layers.h); because every vector-memory operation in the main loop is a DMA with the same look-ahead, no
 //     wait ever drains the pipeline (ordinary loads of B would: vmcnt completes in order);
 //   * epilogue variants: bias + LeakyReLU -> f16 planes (conv2a/3a);  residual + style FiLM + LeakyReLU ->
 //     fp32 rows and/or f16 planes (conv2b/3b, gancraft_base.py:197-200, :213-217).
@@ -30,17 +31,12 @@
 
 #include <cstdlib>
 
+#include "mfma_common.h"
 #include "sdn_common.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(1))) const char glb_char;
 
 constexpr int CH = 256;
 constexpr int A_BYTES = 16384;            // weight fragments of one k-step (8 row blocks, hi + lo)
@@ -72,23 +68,6 @@ struct ConvParams {
     unsigned row_inc, chunk_inc;   // 3x3 k-order increments of the activation offset: tap (r,2) -> (r+1,0), tap (2,2) -> (0,0) of the next chunk
     int gx, gy, n_groups;      // workgroup patches (16 x 16 pixels)
 };
-
-__device__ __forceinline__ f32x16 mfma16(half8 a, half8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float vmax(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// two f32 -> packed f16, round to nearest even: one v_cvt_pk_f16_f32 (new in gfx950)
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ half2v cvt_rtn(float a, float b) {
-    return __builtin_convertvector(float2v{a, b}, half2v);
-}
 
 // ---- the DMA stream ----------------------------------------------------------------------------------------------------
 // k order is channel-chunk major: k = 9*s + tap.  The 9 taps of one 16-channel chunk re-read the same (patch + halo) x 32 B
@@ -188,32 +167,6 @@ __device__ __forceinline__ void issue_piece(const SlotIssue &si, int wave, int l
     if constexpr (PIECE == 1) __builtin_amdgcn_global_load_lds((glb_char *)(si.w + (unsigned)(lane * 16)), (lds_char *)(si.dst + wave * 2048), 16, 1024, 0);
     if constexpr (PIECE == 2) __builtin_amdgcn_global_load_lds((glb_char *)(si.a0 + si.voff), (lds_char *)(si.dst + A_BYTES + wave * B_BYTES), 16, 0, 0);
     if constexpr (PIECE == 3) __builtin_amdgcn_global_load_lds((glb_char *)(si.a1 + si.voff), (lds_char *)(si.dst + A_BYTES + wave * B_BYTES + 1024), 16, 0, 0);
-}
-
-// Fragment reads are inline asm with hand-counted s_waitcnt: behind a pending LDS-DMA the compiler's own wait
-// insertion degrades every LDS wait to lgkmcnt(0), which drains the prefetch issued just before it and exposes one
-// LDS round trip per 6 MFMAs (measured: 1.80 -> see DESIGN.md per 3x3 launch).
-__device__ __forceinline__ unsigned lds_addr(const void *p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
-}
-
-template <int OFF>
-__device__ __forceinline__ void ds_read16(half8 &dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-
-template <int U>
-__device__ __forceinline__ void lds_unit(unsigned slot_lane, half8 (&a)[4]) {
-    ds_read16<U * 4096>(a[0], slot_lane);
-    ds_read16<U * 4096 + 1024>(a[1], slot_lane);
-    ds_read16<U * 4096 + 2048>(a[2], slot_lane);
-    ds_read16<U * 4096 + 3072>(a[3], slot_lane);
-}
-
-template <int N>
-__device__ __forceinline__ void lds_wait() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // One unit (2 row blocks x one k-step, 6 MFMAs).  Behind each MFMA goes ONE piece of other work, so that the

@@ -122,7 +122,7 @@ class TrunkRangeError(RuntimeError):
 
 
 def check_trunk_range(w1, trunk_hidden, shift):
-    """The packed trunk weights (fc_1 .. fc_4) carry 2^shift (field.hip pack_kernel): refuse a style whose weights would
+    """The packed trunk weights (fc_1 .. fc_4) carry 2^shift (mlp_pack.hip pack_kernel): refuse a style whose weights would
     leave f16's range there instead of rendering infinities.  One device->host read per style."""
     tops = [float(w1.abs().max())] + [float(t.abs().max()) * 0.4 for t in trunk_hidden]
     m = max(tops) if all(math.isfinite(v) for v in tops) else float("nan")
@@ -154,7 +154,7 @@ def prepare_style(R):
     off = [lib.sdn_field_const_offset(i) for i in range(6)]
     consts[off[0]:off[0] + 12 * 256] = R.label_bias.reshape(-1)
     consts[off[1]:off[1] + 5 * 256] = torch.stack([R.mod[i][1] for i in (2, 3, 4, 5, 6)]).reshape(-1)
-    # the MLP kernel's activations are LeakyReLU(x) / 0.4 (see field.hip act_stage): the density head absorbs the 0.4
+    # the MLP kernel's activations are LeakyReLU(x) / 0.4 (see mlp_layers.h act_stage): the density head absorbs the 0.4
     consts[off[2]:off[2] + 256] = w["render_net.fc_sigma.weight"].reshape(-1) * 0.4
     consts[off[3]:off[3] + 64] = w["render_net.fc_out_c.bias"]
     consts[off[4]] = w["render_net.fc_sigma.bias"].reshape(-1)[0]

@@ -6,7 +6,7 @@ reference state dict loads unchanged and `imaginaire.generators.scenedreamer.Gen
 calls its own ("Render MLP -- an nn.Module boundary").  Their forward runs
 
     LightningMLP.forward  ->  sdn_render_mlp   (field.hip mlp_kernel<MODE_RAW>: the fused field kernel's layer machinery)
-    SKYMLP.forward        ->  sdn_sky_mlp      (sky_kernel; positional-encoded rows in, or -- when the argument is the
+    SKYMLP.forward        ->  sdn_sky_mlp      (sky.hip sky_kernel; positional-encoded rows in, or -- when the argument is the
                                                 tagged output of this package's voxlib.positional_encoding -- the ray
                                                 directions themselves, the encoding then runs inside the kernel)
     RenderCNN.forward     ->  sdn_conv_head / sdn_conv x4 / sdn_conv_chain (cnn.MfmaCNN)

@@ -1139,7 +1139,7 @@ COLOUR_AUTO_BOUND = 1e-4   # largest net_out difference fp6-corrected vs 3-term 
 FIELD_AUTO_BOUND = 1e-3    # largest net_out error of the fused field vs the fp32 op sequence, whole frame: the north star's radiance
                            # tolerance itself.  Measured on the synthetic weights (tools/dbg_field_err.py): max over the 36 M values of
                            # a 960x540 frame 5 - 6e-5 (rms 4e-6) without early termination, 9e-5 with the default term_eps -- since the
-                           # trunk weights are packed times 2^8 (field.hip TRUNK_SHIFT; before that 5.6 - 8.2e-4, profiles/
+                           # trunk weights are packed times 2^8 (mlp_layers.h TRUNK_SHIFT; before that 5.6 - 8.2e-4, profiles/
                            # r04_gate_survey.jsonl: the lo halves of the split sat in f16's subnormal range, ~20 significant bits, and
                            # the density head sums ~2e3 x its result in cancelling terms).  The kernel's sigma is now as close to an
                            # fp64 evaluation as PyTorch's fp32 one is (1e-4 both).

@@ -436,7 +436,7 @@ def test_trunk_weight_range_is_checked_before_packing():
 
 
 def test_f16_split_loses_bits_to_subnormals_unless_the_weights_are_scaled():
-    """Why pack_kernel stores the trunk weights times 2^TRUNK_SHIFT (field.hip): the lo half of the 3-term split of a weight of
+    """Why pack_kernel stores the trunk weights times 2^TRUNK_SHIFT (mlp_pack.hip): the lo half of the 3-term split of a weight of
     magnitude 0.03 lies in f16's subnormal range.  Emulated with numpy's float16 (which keeps subnormals, like the MFMA
     operands) on four 256 -> 256 layers with fp64 accumulation, so that only the operand representation differs."""
     rng = np.random.default_rng(0)
@@ -536,7 +536,7 @@ def test_ragged_blocked_ray_order_host_side():
 
 
 def test_weight_ring_protocol_with_restarts():
-    """A model of field_kernel's LDS weight ring (csrc/field.hip: Ring, ring_acquire, ring_restart): 4 positions, the DMA runs 3 slots
+    """A model of field_kernel's LDS weight ring (csrc/mlp_layers.h: Ring, ring_acquire, ring_restart): 4 positions, the DMA runs 3 slots
     ahead, a pass streams 46 slots (fc_1: 4, fc_2..fc_6: 8 each, fc_out_c: 2) -- or only the first 28 when its colour branch is
     skipped, after which ring_restart refills the three positions in flight with the NEXT pass's first slots.  Invariants checked over
     random skip patterns: every acquire finds the slot it expects in its position; a refill never lands on the position of the slot

@@ -62,7 +62,7 @@ def test_weight_seeds_and_styles_stay_inside_the_tolerance(scene256, wseed):
               f"(1 vs 3 {c['max_abs_diff_1term_vs_3term']:.1e})")
         assert err < 1e-3
         assert g["path"] == "fused", "the synthetic weight sets are inside the fused field's tolerance"
-        # regression guard of the scaled trunk weights (field.hip TRUNK_SHIFT): with the lo halves of the split in f16's
+        # regression guard of the scaled trunk weights (mlp_layers.h TRUNK_SHIFT): with the lo halves of the split in f16's
         # subnormal range this figure was 5.6e-4 .. 8.2e-4; now the MFMA trunk is as close to fp64 as the fp32 one
         assert g["max_abs_err_vs_fp32"] < 3e-4
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Static check of the hand-counted LDS waits in the MFMA kernels (field.hip, cnn.hip).
+"""Static check of the hand-counted LDS waits in the MFMA kernels (field.hip, sky.hip, cnn_ends.hip, cnn.hip).
 
 The weight-fragment / bias reads are inline-asm ds_read_b128 whose completion hipcc does not track, so nothing but the
 hand-written `s_waitcnt lgkmcnt(N)` keeps an instruction from reading a register whose data has not landed.  This
@@ -18,7 +18,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = {"field.hip": ["-fno-slp-vectorize"], "cnn.hip": []}
+MLP = ["-fno-slp-vectorize"]   # the translation units on csrc/mlp_layers.h (scenedreamer_amd/build.py MLP_FLAGS)
+SRC = {"field.hip": MLP, "sky.hip": MLP, "cnn_ends.hip": MLP, "cnn.hip": []}
 # (mlp_kernel<DBG, CT, MODE>: MODE 0 = features from encode_kernel's buffer (the only one with the AGPR input prefetch), 1 = field_kernel,
 #  2 = field_kernel + per-sample outputs, 3 = LightningMLP.forward as an op; sky_kernel<DBG, SMX, PRE>)
 KERNELS = ("mlp_kernelILi0ELi3ELi0E", "mlp_kernelILi0ELi2ELi0E", "mlp_kernelILi0ELi6ELi0E", "mlp_kernelILi0ELi3ELi1E", "mlp_kernelILi0ELi6ELi1E",
@@ -85,7 +86,7 @@ def run_block(lines, queue, problems, linear=False):
 
 
 def check_kernel(name, lines):
-    """field.hip's kernels: one linear replay in text order (their blocks are laid out in execution order and the loops are
+    """The MLP machinery's kernels: one linear replay in text order (their blocks are laid out in execution order and the loops are
     straight-line bodies; the CFG walk below does not finish on 1 400 reads).  cnn.hip's: every path through the kernel's
     control-flow graph (hipcc rotates its k loop, text order is not execution order)."""
     if not name.startswith("conv_kernel"):
@@ -193,6 +194,7 @@ def check_prefetch_agprs(lines, lo=190, hi=255):
 def main():
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     bad = 0
+    found = set()
     with tempfile.TemporaryDirectory() as tmp:
         for src, flags in SRC.items():
             out = os.path.join(tmp, src + ".s")
@@ -204,10 +206,8 @@ def main():
                 start = next((i for i, l in enumerate(text) if l.startswith("_Z") and k in l and l.rstrip().endswith(":") or
                               (l.startswith("_Z") and k in l and ": " in l)), None)
                 if start is None:
-                    if src == "field.hip" and not k.startswith("conv_kernel"):
-                        print(f"{src}:{k}: NOT FOUND in the compiled ISA (kernel renamed? update KERNELS)")
-                        bad += 1
                     continue
+                found.add(k)
                 end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
                 body = list(enumerate(text[start:end], start + 1))
                 n, problems = check_kernel(k, body)
@@ -220,6 +220,10 @@ def main():
                 for ln, raw, why in problems[:10]:
                     print(f"    line {ln}: {why}: {raw}")
                 bad += len(problems)
+    for k in KERNELS:
+        if k not in found:
+            print(f"{k}: NOT FOUND in the compiled ISA of {', '.join(SRC)} (kernel renamed or moved? update KERNELS / SRC)")
+            bad += 1
     return 1 if bad else 0
 
 

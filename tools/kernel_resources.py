@@ -1,8 +1,8 @@
 """Per-kernel register / scratch / LDS usage of a compiled HIP source (reads the AMDGPU metadata of `hipcc -save-temps`).
 
-    python tools/kernel_resources.py [scenedreamer_amd/csrc/field.hip] [extra hipcc flags...]
+    python tools/kernel_resources.py [scenedreamer_amd/csrc/field.hip | sky.hip | cnn_ends.hip | ...] [extra hipcc flags...]
 
-Used to check that an edit of field.hip did not push a hand-scheduled kernel into scratch spills."""
+Used to check that an edit of the MLP machinery did not push a hand-scheduled kernel into scratch spills."""
 import os
 import re
 import subprocess

@@ -1,6 +1,7 @@
-"""Where a kernel of field.hip touches scratch memory (register spills): line numbers inside the kernel's ISA + the nearest labels.
+"""Where a kernel of field.hip (or another MLP source) touches scratch memory (register spills): line numbers inside the kernel's
+ISA + the nearest labels.
 
-    python tools/spills.py [mangled-name-fragment, default mlp_kernelILi0ELi6ELi1E = field_kernel]
+    python tools/spills.py [mangled-name-fragment, default mlp_kernelILi0ELi6ELi1E = field_kernel] [--src=sky.hip]
 
 tools/kernel_resources.py says HOW MUCH scratch a kernel has; this says where the spills sit (a spill inside a unit of a layer costs
 matrix time, one between passes does not)."""
@@ -18,9 +19,10 @@ args = [a for a in sys.argv[1:] if not a.startswith("-")]
 dump = [a[2:] for a in sys.argv[1:] if a.startswith("-o")]   # -o<file>: write the kernel's ISA there
 verbose = "-v" in sys.argv
 frag = args[0] if args else "mlp_kernelILi0ELi6ELi1E"
-src = os.path.join(ROOT, "scenedreamer_amd/csrc/field.hip")
+name = next((a[6:] for a in sys.argv[1:] if a.startswith("--src=")), "field.hip")   # field.hip, sky.hip, cnn_ends.hip
+src = os.path.join(ROOT, "scenedreamer_amd/csrc", name)
 with tempfile.TemporaryDirectory() as d:
-    cmd = [b._hipcc(), *b.COMMON, *b.SOURCES["field.hip"], "-c", src, "-o", os.path.join(d, "x.o"), "-save-temps"]
+    cmd = [b._hipcc(), *b.COMMON, *b.SOURCES[name], "-c", src, "-o", os.path.join(d, "x.o"), "-save-temps"]
     r = subprocess.run(cmd, cwd=d, capture_output=True, text=True)
     if r.returncode != 0:
         raise SystemExit(r.stderr[-3000:])
