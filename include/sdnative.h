@@ -294,6 +294,38 @@ int sdn_render_mlp(const float *x, const uint8_t *label, const void *packed, con
                    int64_t n_rows, int32_t colour_terms, int32_t n_workgroups, int32_t *ticket, sdn_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The field in plain fp32 (csrc/field_f32.hip): the same call chain as sdn_field_render / sdn_render_mlp --
+ * Generator._forward_perpix / _forward_perpix_sub (scenedreamer.py:285-430), LightningMLP.forward (layers.py:92-126),
+ * volum_rendering_relu (mc_utils.py:154-161) -- with every product of the MLP an f32 x f32 fmaf on the f32-input matrix
+ * instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain).  The weights have fp32's range (no trunk shift, no
+ * restriction on their magnitude) and the result depends on no calibration; it is NOT more accurate than the 3-term f16 split
+ * on weights that fit it, and runs at 1/16 of the f16 matrix rate: the fallback rung, not the default.  Every sample of every
+ * ray that hits something is evaluated (no early termination, no colour-branch skipping, no fp6).
+ */
+size_t sdn_field_f32_packed_weight_bytes(void);
+/* the constant block has the layout of sdn_field_const_offset, with w_sigma = fc_sigma.weight UNSCALED (the f16 kernels'
+ * block stores it times 0.4 for their scaled activation: the two blocks are not interchangeable) */
+size_t sdn_field_f32_consts_floats(void);
+/* the inputs of sdn_field_pack_weights; packed dev, sdn_field_f32_packed_weight_bytes() bytes */
+int sdn_field_pack_weights_f32(const float *w1, const float *const *wh5_host, const float *wc, void *packed,
+                               sdn_stream_t stream);
+/* The arguments of sdn_field_render with the same meaning (window_host incl. blocked 0 / 1 / 2; cam_ori_dev), without
+ * colour_terms, term_eps, passes, strat_division, ticket and aux.  Deterministic sampling only: u_dev must be NULL
+ * (SDN_ERR_UNSUPPORTED otherwise).  packed / consts from sdn_field_pack_weights_f32 / as described above.  Workgroup b of G
+ * evaluates the 32-ray groups b, b + G, ...; groups whose rays all miss are skipped.  net_out is the same bits per ray whatever
+ * the window, the ray order or the schedule. */
+int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024,
+                         const float *table3, uint32_t table_rows, const float *scales_dev, const float *genc_host,
+                         const float *cam_ori_host, const float *voxel_dims_host, const float *lin_dev, const float *u_dev,
+                         int32_t n_rays, int32_t max_blocks, int32_t num_samples, float sample_depth, float dists_scale,
+                         const void *packed, const float *consts, const float *sky_c, const float *sky_avg, float *net_out,
+                         int32_t n_workgroups, const int32_t *window_host, const float *cam_ori_dev, sdn_stream_t stream);
+/* LightningMLP.forward as an op (layers.py:92-126), the arguments of sdn_render_mlp without colour_terms and ticket:
+ * x dev f32 [n_rows,128], label dev u8 [n_rows] -> sigma dev f32 [n_rows] (fc_sigma, :115), c dev f32 [n_rows,64] (fc_out_c, :125) */
+int sdn_render_mlp_f32(const float *x, const uint8_t *label, const void *packed, const float *consts, float *sigma, float *c,
+                       int64_t n_rows, int32_t n_workgroups, sdn_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Render CNN: the convolutions of RenderCNN (imaginaire/generators/gancraft_base.py:175-225, forward :202-225) on MFMA
  * as f16 products with f32 accumulation: 3x3 256->256 (conv2a/2b/3a/3b; taps = 9, cin = 256) and 1x1 cin->256
  * (conv1 64->256, conv4a/4b; taps = 1); the final conv4 (256->3, 1x1) + tanh (:221, :603) is an optional projection

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--seed", type=int, default=8888)
@@ -29,8 +29,14 @@ def main():
     ap.add_argument("--cam_ang", type=float, default=72)
     ap.add_argument("--scene_size", type=int, default=2048)
     ap.add_argument("--scene", default="", help="npz with the fields of the reference's voxel handle (pcg_gen.py:161-174)")
-    ap.add_argument("--mode", default="fused", choices=["fused", "unfused"])
-    args = ap.parse_args()
+    ap.add_argument("--mode", default="fused", choices=["fused", "unfused", "exact"],
+                    help="fused: MFMA kernels behind the per-style precision gates; unfused: the reference's fp32 op sequence on "
+                         "PyTorch; exact: that sequence with the field on the fp32 MFMA kernel (no calibration, any weight range)")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     if world > 1:

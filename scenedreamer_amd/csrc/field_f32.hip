@@ -1,0 +1,453 @@
+// The field in plain fp32 on the f32-input matrix instruction of gfx950 (v_mfma_f32_32x32x2_f32): sample placement ->
+// hash-grid lookup -> LightningMLP -> volume rendering + sky compositing, and LightningMLP.forward as an op of its own.
+// Replaces Generator._forward_perpix / _forward_perpix_sub (imaginaire/generators/scenedreamer.py:285-430) with
+// LightningMLP.forward (imaginaire/model_utils/layers.py:92-126) and volum_rendering_relu (mc_utils.py:154-161), like
+// field.hip -- but every product is an f32 x f32 fmaf: the MFMA result is bit for bit a k-ordered fmaf chain, so the
+// weights have fp32's RANGE (no 2^8-scaled f16 stream, no TrunkRangeError) and the path needs no calibration gate.  What it
+// does NOT buy is accuracy on in-range weights: the 3-term f16 split of field.hip is already as close to fp64 as fp32 is.
+// At 1/16 of the f16 MFMA rate it is the fallback rung for styles the f16 kernels cannot serve, not the default.
+//
+//   field_f32_kernel<FIELD>   per 32-sample tile (8 rays x 4 samples per wave, 4 waves = a 32-ray group per workgroup): the
+//                             encode stage of field_kernel (the same device functions, field_enc.h), fc_1 + label bias ->
+//                             fc_2 .. fc_4 -> fc_sigma, fc_5, fc_6, fc_out_c, then the compositing epilogue of mlp_kernel,
+//                             statement for statement.  Every sample of every ray that hits something is evaluated: no
+//                             early termination, no colour-branch skipping.
+//   field_f32_kernel<RAW>     rows x [n,128] + label u8 [n] -> sigma [n], c [n,64].
+//   pack_f32_kernel           the folded weights in the order the kernel consumes them.
+//
+// Layout.  The MLP is evaluated transposed, W as the A operand (32 output channels per block), the 32 samples as columns.
+// Lane l = (h = l >> 5, j = l & 31) holds A[i = j][k = h] and B[k = h][col j], one f32 each; accumulator register r of
+// lane (h, j) holds channel 8 (r / 4) + 4 h + r % 4 of sample j.  The packed weights order the k-steps of every hidden layer
+// so that k-step r of input block b pairs channels 32 b + 8 (r / 4) + r % 4 (h = 0) and ... + 4 (h = 1): accumulator
+// register r of block b, after bias + LeakyReLU, IS the B operand of that k-step.  Activations never leave the registers
+// and never cross lanes.  The encode stage feeds fc_1 the same way: lane (h, j) blends levels 2 s + h, k-step (s, c) takes
+// channel c of that level from it.
+// Weights: 46 chunks of 32 KiB per pass (4 fc_1, 8 per hidden layer, 2 fc_out_c), the same for every pass.  The four waves
+// share one copy: chunk n + 1 is copied L2 -> LDS (global_load_lds, 16 B per lane, lane-linear image) into the second
+// buffer while chunk n is multiplied; one __syncthreads() per chunk (128 MFMAs of 64 cycles per wave) ends both.
+#include <type_traits>
+
+#include "field_enc.h"
+
+namespace {
+
+constexpr int CHUNK_BYTES = 32768;
+constexpr int CHUNK_FLOATS = CHUNK_BYTES / 4;
+constexpr int N_CHUNKS = 4 + 5 * 8 + 2;     // fc_1 | fc_2 .. fc_6 | fc_out_c; even, so a chunk's buffer is its index & 1
+constexpr size_t PACKED_F32_FLOATS = (size_t)N_CHUNKS * CHUNK_FLOATS;
+static_assert(PACKED_F32_FLOATS == (size_t)HID * FEAT + 5 * HID * HID + OUTC * HID, "the stream holds every weight once");
+
+constexpr int F32_LDS_CONST = 0;                                          // fp32 constant block (the layout of mlp_layers.h)
+constexpr int F32_LDS_SCALES = F32_LDS_CONST + ((C_TOTAL * 4 + 255) / 256) * 256;
+constexpr int F32_LDS_LIN = F32_LDS_SCALES + NLEV * 4;
+constexpr int F32_LDS_LUT = F32_LDS_LIN + MAX_LIN * 4;
+constexpr int F32_LDS_TOTAL = F32_LDS_LUT + 1024;
+
+constexpr int F32_FIELD = 0, F32_RAW = 1;
+
+struct F32Params {
+    const float *wpk;          // packed f32 weights (pack_f32_kernel)
+    const float *consts;       // fp32 constant block, fc_sigma's weights UNSCALED
+    const float *sky_c;        // [n_src, 64]
+    const float *sky_avg;      // dev [64]
+    float *net_out;            // FIELD: [R, 64]; RAW: c [R, 64]
+    int32_t R, ns, nch, n_tiles;
+    RayWindow win;
+    EncParams enc;
+    const float *cam_ori_dev;  // optional dev f32 [3] (overrides enc.ori)
+    const float *x;            // RAW: [R, 128]
+    const uint8_t *label;      // RAW: [R]
+    float *sigma_out;          // RAW: [R]
+};
+
+__device__ __forceinline__ float lrelu(float x) { return x > 0.f ? x : 0.2f * x; }   // F.leaky_relu(x, 0.2)
+
+__device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+template <int K>
+__device__ __forceinline__ void chunk_piece(const char *lane_src, char *dst) {
+    // the immediate offset (a 13-bit signed field: below 4096) is added to the global AND to the LDS address
+    __builtin_amdgcn_global_load_lds((glb_char *)(lane_src + (K / 4) * 4096), (lds_char *)(dst + (K / 4) * 4096), 16, (K % 4) * 1024, 0);
+}
+
+// this wave's quarter of chunk `cp` of the stream -> weight buffer cp & 1: 8 pieces of 1 KiB (64 lanes x 16 B).
+// The source address is a uniform base + this lane's 32-bit byte offset (the saddr form of the load): as 64-bit per-lane
+// pointers hipcc hoists the 8 addresses of every call out of the pass loop and keeps them in scratch memory.
+__device__ __forceinline__ void chunk_fetch(const float *wpk, char *wbuf, int cp, int wave, unsigned lane16) {
+    const char *src = reinterpret_cast<const char *>(wpk) + (size_t)cp * CHUNK_BYTES + wave * 8192;    // uniform
+    char *dst = wbuf + wave * 8192;      // wave-uniform; the DMA adds lane * 16
+    asm volatile("" : "+v"(lane16));
+    chunk_piece<0>(src + lane16, dst); chunk_piece<1>(src + lane16, dst); chunk_piece<2>(src + lane16, dst); chunk_piece<3>(src + lane16, dst);
+    chunk_piece<4>(src + lane16, dst); chunk_piece<5>(src + lane16, dst); chunk_piece<6>(src + lane16, dst); chunk_piece<7>(src + lane16, dst);
+}
+
+// acc[ib] (+)= sum over 16 k-steps of W_chunk[ib][k-step] x b[k-step]: one chunk of an 8-block layer.  A k-step's 2 KiB in the
+// chunk: [output blocks 0-3 | 4-7][lane][4 blocks], so a lane reads two float4 (conflict-free, lane-linear)
+__device__ __forceinline__ void chunk_mul8(const char *wbuf, int lane, const float (&b)[16], f32x16 (&acc)[8]) {
+    const float4 *w = reinterpret_cast<const float4 *>(wbuf) + lane;
+#pragma unroll
+    for (int kk = 0; kk < 16; kk++) {
+        const float4 a0 = w[kk * 128], a1 = w[kk * 128 + 64];
+        acc[0] = mfma_f32(a0.x, b[kk], acc[0]);
+        acc[1] = mfma_f32(a0.y, b[kk], acc[1]);
+        acc[2] = mfma_f32(a0.z, b[kk], acc[2]);
+        acc[3] = mfma_f32(a0.w, b[kk], acc[3]);
+        acc[4] = mfma_f32(a1.x, b[kk], acc[4]);
+        acc[5] = mfma_f32(a1.y, b[kk], acc[5]);
+        acc[6] = mfma_f32(a1.z, b[kk], acc[6]);
+        acc[7] = mfma_f32(a1.w, b[kk], acc[7]);
+    }
+}
+
+// act[ib][r] = LeakyReLU(acc[ib][r] + bias[channel]), acc = 0.  Registers 4 g .. 4 g + 3 of block ib = channels 32 ib + 8 g + 4 h + e
+__device__ __forceinline__ void activate(f32x16 (&acc)[8], const float *bias, int h, float (&act)[8][16]) {
+#pragma unroll
+    for (int ib = 0; ib < 8; ib++)
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const float4 bv = *reinterpret_cast<const float4 *>(bias + 32 * ib + 8 * g + 4 * h);
+            act[ib][4 * g + 0] = lrelu(acc[ib][4 * g + 0] + bv.x);
+            act[ib][4 * g + 1] = lrelu(acc[ib][4 * g + 1] + bv.y);
+            act[ib][4 * g + 2] = lrelu(acc[ib][4 * g + 2] + bv.z);
+            act[ib][4 * g + 3] = lrelu(acc[ib][4 * g + 3] + bv.w);
+        }
+#pragma unroll
+    for (int ib = 0; ib < 8; ib++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[ib][r] = 0.f;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
+    constexpr bool RAW = MODE == F32_RAW;
+    // The two weight buffers are two OBJECTS on purpose: hipcc's wait insertion then knows that the LDS-DMA into one cannot
+    // alias the fragment reads from the other and waits for the DMA (vmcnt) only at the __syncthreads() that ends the chunk.
+    // As halves of one array every first fragment read of a chunk waited for the prefetch issued just before it.
+    __shared__ __attribute__((aligned(1024))) char wb0[CHUNK_BYTES];
+    __shared__ __attribute__((aligned(1024))) char wb1[CHUNK_BYTES];
+    __shared__ __attribute__((aligned(1024))) char lds[F32_LDS_TOTAL];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int h = lane >> 5, j = lane & 31, q = j & 3;
+    const unsigned lane16 = lane * 16;
+
+    chunk_fetch(p.wpk, wb0, 0, wave, lane16);
+    float *cst = reinterpret_cast<float *>(lds + F32_LDS_CONST);
+    static_assert(C_SKY_AVG + OUTC == C_TOTAL, "sky_avg is the tail of the constant block");
+    for (int i = threadIdx.x; i < C_TOTAL; i += 256)
+        cst[i] = (p.sky_avg && i >= C_SKY_AVG) ? p.sky_avg[i - C_SKY_AVG] : p.consts[i];
+    EncParams enc = p.enc;
+    if constexpr (!RAW) {   // the encode stage reads its small tables from LDS, as in field_kernel
+        float *e_scales = reinterpret_cast<float *>(lds + F32_LDS_SCALES), *e_lin = reinterpret_cast<float *>(lds + F32_LDS_LIN);
+        uint8_t *e_lut = reinterpret_cast<uint8_t *>(lds + F32_LDS_LUT);
+        if (threadIdx.x < NLEV) e_scales[threadIdx.x] = p.enc.scales[threadIdx.x];
+        if (threadIdx.x < p.enc.ns + 1) e_lin[threadIdx.x] = p.enc.lin[threadIdx.x];
+        for (int i = threadIdx.x; i < 1024; i += 256) e_lut[i] = p.enc.lut[i];
+        enc.scales = e_scales; enc.lin = e_lin; enc.lut = e_lut;
+        if (p.cam_ori_dev) {
+            enc.ori[0] = p.cam_ori_dev[0]; enc.ori[1] = p.cam_ori_dev[1]; enc.ori[2] = p.cam_ori_dev[2];
+        }
+    }
+    __syncthreads();   // chunk 0 and the tables are in place.  From here on: at a pass's start chunk 0 sits in buffer 0
+
+    const int n_groups = (p.n_tiles + 3) >> 2;
+    for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int tile = grp * 4 + wave;
+        const bool tile_ok = tile < p.n_tiles;
+        const int ray = tile * RAYS_PER_TILE + (j >> 2);
+        const bool ray_ok = !RAW && tile_ok && ray < p.R && p.win.valid(ray);
+        const int rl = ray_ok ? ray : p.R - 1;
+        const int rr = RAW ? 0 : enc.win.src(rl);
+        uint8_t flag = 0;                                  // bit 0 sky_only, bit 1 nosky
+        if constexpr (!RAW) flag = (ray_ok && enc.voxel_id[(size_t)rr * enc.M] != 0) ? (uint8_t)0 : (uint8_t)1;   // scenedreamer.py:337
+        // a group none of whose 32 rays hits anything is skipped: every weight is exactly zero (:376)
+        const bool grp_hit = RAW ? true : __syncthreads_or(!(flag & 1)) != 0;
+        bool gnd = false;
+        float outq[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        float carry = 0.f, tsum = 0.f;
+
+        for (int ch = 0; grp_hit && ch < p.nch; ch++) {
+            int lab;
+            float dist = 0.f;
+            float feat[8][8];
+            const long row = (long)(tile_ok ? tile : 0) * 256 + ch * 32 + j;   // RAW: this lane's row
+            if constexpr (RAW) {
+                const long rc = row < p.R ? row : (long)p.R - 1;               // (lanes past the end evaluate the last row, store nothing)
+                lab = p.label[rc];
+                const float *src = p.x + rc * FEAT + 8 * h;                    // k-step (s, c), lane half h = feature 16 s + 8 h + c
+#pragma unroll
+                for (int s = 0; s < 8; s++) {
+                    const float4 a = *reinterpret_cast<const float4 *>(src + 16 * s), b = *reinterpret_cast<const float4 *>(src + 16 * s + 4);
+                    feat[s][0] = a.x; feat[s][1] = a.y; feat[s][2] = a.z; feat[s][3] = a.w;
+                    feat[s][4] = b.x; feat[s][5] = b.y; feat[s][6] = b.z; feat[s][7] = b.w;
+                }
+            } else {
+                RayBoxes rb;
+                float dd[3];
+                enc_load_ray(enc, rr, rb, dd);
+                const EncSample es = enc_place(enc, rb, dd, rl, ch * SAMP_PER_STEP + (j & 3), ray_ok);
+                gnd = gnd || es.gnd;
+                lab = es.label;
+                dist = es.dist;
+                const bool use_feat = !(flag & 1);
+                // Gathers in flight per lane: 2 levels (32 x 16 B), then one at a time (field_kernel: 4 levels).  The features stay
+                // f32 here -- 64 registers per lane by the end of the stage -- and a pass is 377 k matrix cycles long: a few more round
+                // trips to L2 cost little, spilling would cost more
+                auto gather = [&](auto nb, int s0) {
+                    constexpr int NB = decltype(nb)::value;
+                    float res[NB][8];
+                    enc_levels<NB>(enc, es, s0, h, use_feat, res);
+#pragma unroll
+                    for (int t = 0; t < NB; t++)
+#pragma unroll
+                        for (int c = 0; c < 8; c++) feat[s0 + t][c] = res[t][c];
+                };
+                gather(std::integral_constant<int, 2>{}, 0);
+                gather(std::integral_constant<int, 2>{}, 2);
+#pragma unroll
+                for (int s = 4; s < 8; s++) gather(std::integral_constant<int, 1>{}, s);
+            }
+            lab = lab < NLAB ? lab : NLAB - 1;   // (the table has 12 rows; a label outside it must not read past the block)
+
+            f32x16 acc[8];
+#pragma unroll
+            for (int ib = 0; ib < 8; ib++) acc[ib] = zero16();
+            float act[8][16];
+            // ---- fc_1: chunks 0..3, chunk c = levels pairs s = 2 c, 2 c + 1 x 8 channels -------------------------------------
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                chunk_fetch(p.wpk, (c & 1) ? wb0 : wb1, c + 1, wave, lane16);
+                float b[16];
+#pragma unroll
+                for (int kk = 0; kk < 16; kk++) b[kk] = feat[2 * c + (kk >> 3)][kk & 7];
+                chunk_mul8((c & 1) ? wb1 : wb0, lane, b, acc);
+                __syncthreads();
+            }
+            activate(acc, cst + C_LABEL_BIAS + lab * HID, h, act);     // fc_1(x) + fc_m_a(m), layers.py:105-109
+            // ---- fc_2 .. fc_6: chunks 4 + 8 l + b, b = input block --------------------------------------------------------------
+            float part = 0.f;
+#pragma unroll 1
+            for (int l = 0; l < 5; l++) {
+#pragma unroll
+                for (int b = 0; b < 8; b++) {
+                    chunk_fetch(p.wpk, (b & 1) ? wb0 : wb1, 4 + 8 * l + b + 1, wave, lane16);
+                    chunk_mul8((b & 1) ? wb1 : wb0, lane, act[b], acc);
+                    __syncthreads();
+                }
+                activate(acc, cst + C_BETA + l * HID, h, act);
+                if (l == 2) {   // fc_sigma on fc_4's activations (layers.py:115): this lane's 128 channels, then the other half's
+                    const float *wsig = cst + C_WSIGMA;
+#pragma unroll
+                    for (int ib = 0; ib < 8; ib++)
+#pragma unroll
+                        for (int g = 0; g < 4; g++) {
+                            const float4 wv = *reinterpret_cast<const float4 *>(wsig + 32 * ib + 8 * g + 4 * h);
+                            part = fmaf(wv.x, act[ib][4 * g + 0], part);
+                            part = fmaf(wv.y, act[ib][4 * g + 1], part);
+                            part = fmaf(wv.z, act[ib][4 * g + 2], part);
+                            part = fmaf(wv.w, act[ib][4 * g + 3], part);
+                        }
+                }
+            }
+            // ---- fc_out_c: chunks 44, 45 = input blocks 0-3, 4-7; a k-step is [lane][2 output blocks] ----------------------------
+            f32x16 col[2];
+            col[0] = zero16();
+            col[1] = zero16();
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                chunk_fetch(p.wpk, c ? wb0 : wb1, c == 0 ? N_CHUNKS - 1 : 0, wave, lane16);   // (the last one: chunk 0 of the next pass)
+                const float2v *w = reinterpret_cast<const float2v *>(c ? wb1 : wb0) + lane;
+#pragma unroll
+                for (int kk = 0; kk < 64; kk++) {
+                    const float2v a = w[kk * 64];
+                    col[0] = mfma_f32(a[0], act[4 * c + (kk >> 4)][kk & 15], col[0]);
+                    col[1] = mfma_f32(a[1], act[4 * c + (kk >> 4)][kk & 15], col[1]);
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++)
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const float4 bv = *reinterpret_cast<const float4 *>(cst + C_BC + 32 * ib + 8 * g + 4 * h);
+                    col[ib][4 * g + 0] += bv.x; col[ib][4 * g + 1] += bv.y; col[ib][4 * g + 2] += bv.z; col[ib][4 * g + 3] += bv.w;
+                }
+            const float sigma = part + __shfl_xor(part, 32) + cst[C_BSIGMA];
+            if constexpr (RAW) {   // LightningMLP.forward's outputs for this lane's row: (sigma, c), layers.py:115, :125
+                if (tile_ok && row < p.R) {
+                    if (h == 0) p.sigma_out[row] = sigma;
+#pragma unroll
+                    for (int ib = 0; ib < 2; ib++)
+#pragma unroll
+                        for (int g4 = 0; g4 < 4; g4++)
+                            *reinterpret_cast<float4 *>(p.net_out + (size_t)row * OUTC + 32 * ib + 8 * g4 + 4 * h) =
+                                make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
+                }
+                continue;
+            }
+            // ---- volume rendering (mc_utils.py:154-161) over the 4 samples of each ray in this pass: mlp_kernel's statements ----
+            const float fe = fmaxf(sigma, 0.f) * dist;
+            float incl = fe;
+            float up = quad_dpp<QUAD_UP1>(incl);
+            if (q >= 1) incl += up;
+            up = quad_dpp<QUAD_UP2>(incl);
+            if (q >= 2) incl += up;
+            float ex = quad_dpp<QUAD_UP1>(incl);
+            if (q == 0) ex = 0.f;
+            const float excl = carry + ex;
+            const float wgt = (1.f - __expf(-fe)) * __expf(-excl);
+            carry += quad_dpp<QUAD_LAST>(incl);
+            tsum += wgt;
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float rgb = fminf(fmaxf(col[ib][r], -1.f), 1.f) + 1.f;  // scenedreamer.py:408
+                    float v = wgt * rgb;
+                    v += quad_dpp<QUAD_XOR1>(v);   // sum over the 4 samples of the ray held by this quad
+                    v += quad_dpp<QUAD_XOR2>(v);
+                    if ((r >> 2) == q) outq[ib][r & 3] += v;
+                }
+        }
+
+        // ---- blend the sky, store: mlp_kernel's statements --------------------------------------------------------------------
+        if constexpr (!RAW) {
+            tsum += quad_dpp<QUAD_XOR1>(tsum);
+            tsum += quad_dpp<QUAD_XOR2>(tsum);
+            // (the ray's addresses are derived again from an opaque copy of its index: computed at the group's start they would
+            //  be carried through every pass, in scratch memory)
+            int ray_e = rl;
+            asm volatile("" : "+v"(ray_e));
+            const int rr_e = enc.win.src(ray_e);
+            {   // nosky = the ray's last intersection is a voxel, or one of its samples lies at world x <= 1 (:335, :382)
+                int g = (int)gnd;
+                g |= quad_dpp<QUAD_XOR1>(g);
+                g |= quad_dpp<QUAD_XOR2>(g);
+                const bool last_hit = ray_ok && enc.voxel_id[(size_t)rr_e * enc.M + (enc.M - 1)] != 0;
+                if (last_hit || g) flag |= 2;
+            }
+            const bool sky_only = flag & 1, nosky = flag & 2;
+            if (sky_only) tsum = 0.f;  // scenedreamer.py:376
+            const float sky_w = 1.f - tsum;
+            if (ray_ok) {
+#pragma unroll
+                for (int ib = 0; ib < 2; ib++) {
+                    const int f0 = 32 * ib + 8 * q + 4 * h;   // this lane owns features f0 .. f0+3 of its ray
+                    const float4 sc = *reinterpret_cast<const float4 *>(p.sky_c + (size_t)rr_e * OUTC + f0);
+                    const float4 sa = *reinterpret_cast<const float4 *>(cst + C_SKY_AVG + f0);
+                    const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, sav[4] = {sa.x, sa.y, sa.z, sa.w};
+                    float o[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const float sky = nosky ? (scv[e] * 0.f + sav[e]) : scv[e];          // :401, mask in {0,1}
+                        const float rgb_sky = fminf(fmaxf(sky, -1.f), 1.f) + 1.f;
+                        o[e] = (sky_only ? 0.f : outq[ib][e]) + sky_w * rgb_sky - 1.f;       // :410-413
+                    }
+                    *reinterpret_cast<float4 *>(p.net_out + (size_t)p.win.out_row(ray_e) * OUTC + f0) = make_float4(o[0], o[1], o[2], o[3]);
+                }
+            }
+        }
+    }
+    __syncthreads();   // (a pass's last fetch -- chunk 0 for a pass that never came -- lands before the LDS is released)
+}
+
+// ---- the packed stream --------------------------------------------------------------------------------------------------------
+struct PackF32Params {
+    const float *w1;      // [256,128]
+    const float *wh[5];   // [256,256] each, W * alpha already folded
+    const float *wc;      // [64,256]
+    float *out;
+};
+
+// channel that accumulator register r of lane half h holds inside its 32-channel block = k of k-step r of that input block
+__host__ __device__ inline int kmap_f32(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
+
+__global__ __launch_bounds__(256) void pack_f32_kernel(const PackF32Params p) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;   // one thread per float of the stream
+    if (g >= PACKED_F32_FLOATS) return;
+    const int cp = (int)(g / CHUNK_FLOATS), rem = (int)(g % CHUNK_FLOATS);
+    float v;
+    if (cp < N_CHUNKS - 2) {
+        const int kk = rem / 512, in = rem % 512, ib = 4 * (in / 256) + (in & 3), lane = (in % 256) / 4, h = lane >> 5, row = 32 * ib + (lane & 31);
+        if (cp < 4) v = p.w1[(size_t)row * FEAT + 16 * (2 * cp + (kk >> 3)) + 8 * h + (kk & 7)];
+        else v = p.wh[(cp - 4) / 8][(size_t)row * HID + 32 * ((cp - 4) % 8) + kmap_f32(kk, h)];
+    } else {
+        const int kk = rem / 128, in = rem % 128, ib = in & 1, lane = in / 2, h = lane >> 5, row = 32 * ib + (lane & 31);
+        v = p.wc[(size_t)row * HID + 32 * (4 * (cp - (N_CHUNKS - 2)) + (kk >> 4)) + kmap_f32(kk & 15, h)];
+    }
+    p.out[g] = v;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sdn_field_f32_packed_weight_bytes(void) { return PACKED_F32_FLOATS * sizeof(float); }
+size_t sdn_field_f32_consts_floats(void) { return C_TOTAL; }
+
+int sdn_field_pack_weights_f32(const float *w1, const float *const *wh5_host, const float *wc, void *packed, sdn_stream_t stream) {
+    SDN_REQUIRE(w1 && wh5_host && wc && packed, "sdn_field_pack_weights_f32: null pointer");
+    PackF32Params p;
+    p.w1 = w1;
+    for (int i = 0; i < 5; i++) {
+        SDN_REQUIRE(wh5_host[i], "sdn_field_pack_weights_f32: null hidden weight");
+        p.wh[i] = wh5_host[i];
+    }
+    p.wc = wc;
+    p.out = (float *)packed;
+    hipLaunchKernelGGL(pack_f32_kernel, dim3((unsigned)sdn::div_up<size_t>(PACKED_F32_FLOATS, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return sdn::check_launch("sdn_field_pack_weights_f32");
+}
+
+static int f32_workgroups(const F32Params &p, int32_t n_workgroups) {
+    const int wg = n_workgroups > 0 ? n_workgroups : 256;
+    const int groups = sdn::div_up(p.n_tiles, 4);
+    return wg > groups ? groups : wg;
+}
+
+int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024, const float *table3,
+                         uint32_t table_rows, const float *scales_dev, const float *genc_host, const float *cam_ori_host,
+                         const float *voxel_dims_host, const float *lin_dev, const float *u_dev, int32_t n_rays, int32_t max_blocks,
+                         int32_t num_samples, float sample_depth, float dists_scale, const void *packed, const float *consts,
+                         const float *sky_c, const float *sky_avg, float *net_out, int32_t n_workgroups, const int32_t *window_host,
+                         const float *cam_ori_dev, sdn_stream_t stream) {
+    if (!(packed && consts && sky_c && net_out)) return sdn::fail(SDN_ERR_INVALID, "sdn_field_render_f32: null pointer");
+    if (u_dev) return sdn::fail(SDN_ERR_UNSUPPORTED, "sdn_field_render_f32: deterministic sampling only (u_dev must be NULL)");
+    static const float zero3[3] = {0.f, 0.f, 0.f};
+    if (cam_ori_dev && !cam_ori_host) cam_ori_host = zero3;
+    F32Params p;
+    if (int rc = fill_enc(p.enc, "sdn_field_render_f32", voxel_id, depth2, raydirs, lut1024, table3, table_rows, scales_dev, genc_host,
+                          cam_ori_host, voxel_dims_host, lin_dev, nullptr, n_rays, max_blocks, num_samples, sample_depth, dists_scale, 0))
+        return rc;
+    int32_t launch_rays = n_rays;
+    if (int rc = set_window(p.win, window_host, n_rays, "sdn_field_render_f32", &launch_rays)) return rc;
+    p.enc.win = p.win;
+    p.R = p.enc.R = launch_rays;     // (a ragged blocked window walks its whole block grid: the extra positions are no rays)
+    p.ns = num_samples;
+    p.nch = p.enc.nch;
+    p.n_tiles = p.enc.n_tiles = sdn::div_up(launch_rays, RAYS_PER_TILE);
+    p.wpk = (const float *)packed; p.consts = consts; p.sky_c = sky_c; p.sky_avg = sky_avg; p.net_out = net_out;
+    p.cam_ori_dev = cam_ori_dev;
+    p.x = nullptr; p.label = nullptr; p.sigma_out = nullptr;
+    hipLaunchKernelGGL((field_f32_kernel<F32_FIELD>), dim3(f32_workgroups(p, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
+    return sdn::check_launch("sdn_field_render_f32");
+}
+
+int sdn_render_mlp_f32(const float *x, const uint8_t *label, const void *packed, const float *consts, float *sigma, float *c,
+                       int64_t n_rows, int32_t n_workgroups, sdn_stream_t stream) {
+    SDN_REQUIRE(x && label && packed && consts && sigma && c, "sdn_render_mlp_f32: null pointer");
+    SDN_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 31), "sdn_render_mlp_f32: n_rows must be in [1, 2^31)");
+    F32Params p;
+    p.wpk = (const float *)packed; p.consts = consts; p.sky_c = nullptr; p.sky_avg = nullptr; p.net_out = c;
+    p.R = (int32_t)n_rows; p.ns = 32; p.nch = 8;
+    p.n_tiles = (int32_t)((n_rows + 255) / 256);
+    p.win.n_src = p.R; p.win.pitch = 0; p.win.first = 0; p.win.cols = 0; p.win.ray0 = 0; p.win.tiled_bx = 0; p.win.rows = 0;
+    p.enc = EncParams{};
+    p.cam_ori_dev = nullptr;
+    p.x = x; p.label = label; p.sigma_out = sigma;
+    hipLaunchKernelGGL((field_f32_kernel<F32_RAW>), dim3(f32_workgroups(p, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
+    return sdn::check_launch("sdn_render_mlp_f32");
+}
+
+}  // extern "C"

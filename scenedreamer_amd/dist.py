@@ -349,7 +349,8 @@ def agree_precision(renderer, pose, resolution_hw, num_samples, group=None, more
     (Renderer.adopt_precision) -- bands of one frame, or frames of one trajectory, never mix precisions.  Explicit settings
     stay as they are.  more_poses: further poses measured and MAX-combined, as the single-process trajectory loop does with
     the middle pose of its trajectory (Renderer.calibrate_style) -- the same policy, so a multi-rank job cannot adopt a cheaper
-    rung than one process would for the same style and trajectory.  Returns {"cnn": cnn_calibration, "field": field_gate}."""
+    rung than one process would for the same style and trajectory.  What a closed gate selects is Renderer.fallback ("unfused" or
+    "exact"), read by adopt_precision after the reduction: every rank must have been given the same value.  Returns {"cnn": cnn_calibration, "field": field_gate}."""
     renderer.cnn_calibration = None
     renderer.field_gate = None
     renderer.colour_terms_auto = None

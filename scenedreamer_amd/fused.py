@@ -162,6 +162,86 @@ def prepare_style(R):
     return R._fused_style
 
 
+def prepare_style_f32(R):
+    """The folded MLP weights as plain f32 in the order field_f32_kernel consumes them + its constant block (once per style,
+    dropped by set_style_code like prepare_style's).  No trunk shift, no f16 anywhere: no restriction on the weights' range."""
+    lib = _lib()
+    w = R.w
+    packed = torch.empty(lib.sdn_field_f32_packed_weight_bytes(), dtype=torch.uint8, device=R.dev)
+    wh = [R.mod[i][0].contiguous() for i in (2, 3, 4, 5, 6)]
+    ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in wh])
+    w1 = w["render_net.fc_1.weight"].contiguous()
+    wc = w["render_net.fc_out_c.weight"].contiguous()
+    with torch.cuda.device(R.dev):
+        capi.check(lib.sdn_field_pack_weights_f32(w1.data_ptr(), ptrs, wc.data_ptr(), packed.data_ptr(), _stream(R.dev)),
+                   "sdn_field_pack_weights_f32")
+    consts = torch.zeros(lib.sdn_field_f32_consts_floats(), dtype=torch.float32, device=R.dev)
+    off = [lib.sdn_field_const_offset(i) for i in range(6)]
+    consts[off[0]:off[0] + 12 * 256] = R.label_bias.reshape(-1)
+    consts[off[1]:off[1] + 5 * 256] = torch.stack([R.mod[i][1] for i in (2, 3, 4, 5, 6)]).reshape(-1)
+    consts[off[2]:off[2] + 256] = w["render_net.fc_sigma.weight"].reshape(-1)      # unscaled: the activations are LeakyReLU itself
+    consts[off[3]:off[3] + 64] = w["render_net.fc_out_c.bias"]
+    consts[off[4]] = w["render_net.fc_sigma.bias"].reshape(-1)[0]
+    R._fused_style_f32 = dict(packed=packed, consts=consts, keep=(wh, w1, wc))
+    return R._fused_style_f32
+
+
+def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None):
+    """field_render's result from the fp32 kernel (csrc/field_f32.hip): sample placement + hash-grid lookup by the same device
+    functions, the MLP as f32 x f32 fmaf chains on the f32-input MFMA, every sample evaluated.  Deterministic sampling only.
+    The weights need not fit f16 (no TrunkRangeError) and nothing here is calibrated; on weights the f16 kernels accept it is
+    NOT closer to the reference than they are -- it is the native fallback for the styles they do not serve.
+    Arguments as for field_render (tensors only); net_out [window.n_rays, 64] in the window's row-major order."""
+    sc = R._fused_scene or prepare_scene(R)
+    st = getattr(R, "_fused_style_f32", None) or prepare_style_f32(R)
+    if window is None:
+        window = Window(vid.shape[0])
+    n_rays = window.n_rays
+    vid, d2, rd, sky_c = vid.contiguous(), d2.contiguous(), rd.contiguous(), sky_c.contiguous()
+    for t, rows, what in ((vid, 0, "voxel_id"), (d2, 1, "depth2"), (rd, 0, "raydirs"), (sky_c, 0, "sky_c")):
+        if not (t.is_cuda and t.device == R.dev and t.shape[rows] == window.n_src):
+            raise ValueError(f"{what} must hold the window's {window.n_src} source rays on {R.dev}")
+    sky_avg = torch.as_tensor(sky_avg).reshape(-1).to(device=R.dev, dtype=torch.float32).contiguous()
+    assert sky_avg.numel() == 64
+    net_out = torch.empty((n_rays, 64), dtype=torch.float32, device=R.dev)
+    buf = R.__dict__.setdefault("_fused_lin", {})
+    lin = buf.get(("det", ns))
+    if lin is None:
+        lin = buf[("det", ns)] = torch.linspace(0, 1, ns + 3)[1:-1].contiguous().to(R.dev)        # mc_utils.py:120
+    ori_dev = None
+    if isinstance(cam_ori, torch.Tensor) and cam_ori.is_cuda:
+        ori_dev = cam_ori.detach().reshape(-1).to(torch.float32).contiguous()
+        assert ori_dev.numel() == 3 and ori_dev.device == R.dev
+        ori = np.zeros(3, np.float32)
+    else:
+        ori = np.asarray(cam_ori.detach().cpu().numpy() if isinstance(cam_ori, torch.Tensor) else cam_ori, np.float32).reshape(3)
+    with torch.cuda.device(R.dev):
+        rc = _lib().sdn_field_render_f32(vid.data_ptr(), d2.data_ptr(), rd.data_ptr(), sc["lut"].data_ptr(), sc["table3"].data_ptr(),
+                                         sc["T"], sc["scales"].data_ptr(), sc["genc"].ctypes.data, ori.ctypes.data,
+                                         sc["dims"].ctypes.data, lin.data_ptr(), None, n_rays, R.M, ns, R.sample_depth,
+                                         R.dists_scale, st["packed"].data_ptr(), st["consts"].data_ptr(), sky_c.data_ptr(),
+                                         sky_avg.data_ptr(), net_out.data_ptr(), 0, window.host(0, n_rays, True),
+                                         ori_dev.data_ptr() if ori_dev is not None else None, _stream(R.dev))
+    capi.check(rc, "sdn_field_render_f32")
+    return net_out
+
+
+def render_mlp_exact(R, x, label):
+    """LightningMLP.forward for rows x [n,128] f32 and labels u8 [n] by the fp32 kernel: (sigma [n], c [n,64])."""
+    st = getattr(R, "_fused_style_f32", None) or prepare_style_f32(R)
+    x, label = x.contiguous(), label.contiguous()
+    n = x.shape[0]
+    assert x.dtype == torch.float32 and tuple(x.shape) == (n, 128) and label.dtype == torch.uint8 and label.numel() == n
+    assert x.device == R.dev == label.device
+    sigma = torch.empty(n, dtype=torch.float32, device=R.dev)
+    c = torch.empty((n, 64), dtype=torch.float32, device=R.dev)
+    if n:
+        with torch.cuda.device(R.dev):
+            capi.check(_lib().sdn_render_mlp_f32(x.data_ptr(), label.data_ptr(), st["packed"].data_ptr(), st["consts"].data_ptr(),
+                                                 sigma.data_ptr(), c.data_ptr(), n, 0, _stream(R.dev)), "sdn_render_mlp_f32")
+    return sigma, c
+
+
 def _buffers(R, n_rays, ns, slot=0):
     key = (n_rays, ns, slot)
     cache = R.__dict__.setdefault("_fused_buf", {})

@@ -49,7 +49,7 @@ class Backend:
         self.dev = None
         self.w = {}
         self.M, self.sample_depth, self.dists_scale, self.pad = 6, 3.0, 0.25, 0
-        self._fused_scene = self._fused_style = self._fused_sky = None
+        self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = None
         self.cnn_calibration = None
         self._bound = {}
         self._zkey = {}
@@ -76,7 +76,7 @@ class Backend:
         if self.dev is not None and self.dev != dev:
             self.w = {k: v for k, v in self.w.items() if k.startswith(prefix)}
             self._bound.clear()
-            self._fused_scene = self._fused_style = self._fused_sky = None
+            self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = None
             self.__dict__.pop("_mfma_cnns", None)
         self.dev = dev
         self._bound[prefix] = (module, key)
@@ -136,7 +136,10 @@ def _cuda_f32(*tensors):
 # native forwards (mixins: they only rely on the reference's attribute names)
 # ---------------------------------------------------------------------------------------------------------------------
 class LightningMLPNative:
-    """forward(x [N,H,W,M,128], raydir (unused: viewdir_dim = 0), z [N,style], m [N,H,W,M,12] one-hot) -> (sigma [..,1], c [..,64])."""
+    """forward(x [N,H,W,M,128], raydir (unused: viewdir_dim = 0), z [N,style], m [N,H,W,M,12] one-hot) -> (sigma [..,1], c [..,64]).
+    Opt-in `module.sdn_exact = True` (or SDN_MLP_EXACT=1): the call runs on the fp32 MFMA kernel (sdn_render_mlp_f32) -- weights of
+    any range natively (no TrunkRangeError detour through _forward_composite), at 1/16 of the f16 matrix rate; no accuracy gain on
+    weights the default kernel accepts."""
     _sdn_native = True
 
     def native_reason(self, x, raydir, z, m):
@@ -184,9 +187,19 @@ class LightningMLPNative:
         c = torch.empty((n, h, w_, ms, 64), dtype=torch.float32, device=x.device)
         if rows == 0:
             return sigma, c
+        # opt-in: the call on the fp32 kernel (sdn_render_mlp_f32) -- any weight range, nothing calibrated, 1/16 of the matrix rate
+        exact = bool(self.__dict__.get("sdn_exact", os.environ.get("SDN_MLP_EXACT", "0") not in ("0", "", "false")))
         with torch.no_grad():
             for i in range(n):
                 B.style("render_net.", z, i, fold_render_net)
+                if exact:
+                    xi = x[i].reshape(rows, 128)
+                    lab = (m[i].reshape(rows, 12).argmax(dim=-1).to(torch.uint8) if self.use_seg
+                           else torch.zeros(rows, dtype=torch.uint8, device=x.device))
+                    si, ci = fused.render_mlp_exact(B, xi, lab)
+                    sigma[i].reshape(-1).copy_(si)
+                    c[i].reshape(rows, 64).copy_(ci)
+                    continue
                 try:
                     st = B._fused_style or fused.prepare_style(B)
                 except fused.TrunkRangeError as e:        # weights the packed f16 stream cannot hold: the reference's arithmetic

@@ -60,6 +60,7 @@ def fold_render_net(R, z):
         else:
             R.label_bias = b1.expand(12, -1).contiguous()
     R._fused_style = None
+    R._fused_style_f32 = None
 
 
 def fold_sky_net(R, z):
@@ -77,6 +78,16 @@ def fold_denoiser(R, z):
 
 
 class Renderer:
+    # What a closed precision gate selects (adopt_precision): "unfused" = the reference's fp32 op sequence on PyTorch, field, sky
+    # MLP and CNN; "exact" = the same with the field on the fp32 MFMA kernel (fused.field_exact).  Every rank of a distributed job
+    # must be given the same value (dist.agree_precision).
+    fallback = "unfused"
+
+    def _fallback_mode(self):
+        if self.fallback not in ("unfused", "exact"):
+            raise ValueError(f"Renderer.fallback must be 'unfused' or 'exact', not {self.fallback!r}")
+        return self.fallback
+
     def __init__(self, weights, scene, device="cuda", num_blocks_early_stop=6, sample_depth=3.0, dists_scale=0.25,
                  pad=30):
         self.dev = torch.device(device)
@@ -459,7 +470,7 @@ class Renderer:
         ect, et = meas["explicit_colour"], meas["explicit_cnn"]
         ct = ect if ect is not None else (6 if meas["colour_diff"] <= COLOUR_AUTO_BOUND else 3)
         ferr = meas["field_err"][ct]
-        path = "fused" if ferr <= FIELD_AUTO_BOUND else "unfused"
+        path = "fused" if ferr <= FIELD_AUTO_BOUND else self._fallback_mode()
         bound = float(getattr(self, "cnn_auto_bound", None) or CNN_AUTO_BOUND)
         ierr = meas["image_err"]
         cal = None
@@ -472,7 +483,7 @@ class Renderer:
                     t = cand
                     break
             if t == 3 and ierr[3] > IMAGE_AUTO_BOUND:
-                path = "unfused"
+                path = self._fallback_mode()
             cal = {"terms3x3": t, "max_abs_diff_1term_vs_3term": meas["cnn_diff"], "bound": bound,
                    "max_abs_diff_vs_3term": {str(k): v for k, v in diffs.items()},
                    "image_err_vs_fp32": {("1-term" if k == 1 else "3-term" if k == 3 else str(k)): v for k, v in ierr.items()},
@@ -546,7 +557,7 @@ class Renderer:
 
     def field_falls_back(self):
         g = getattr(self, "field_gate", None)
-        return bool(g) and g.get("path") == "unfused"
+        return bool(g) and g.get("path") in ("unfused", "exact")
 
     def _cnn_form(self, terms3x3):
         from .cnn import MfmaCNN, form_key
@@ -613,6 +624,8 @@ class Renderer:
     def compute_dtype(self, mode):
         if mode == "unfused":
             return "f32"
+        if mode == "exact":
+            return "f32 (field: hash grid + f32-input MFMA with f32 accumulate; sky MLP and render CNN: PyTorch)"
         from . import fused
         ct, _ = fused.precision_profile(self)
         cal = getattr(self, "cnn_calibration", None)
@@ -828,7 +841,7 @@ class Renderer:
         f, c, cam_res = frame_intrinsics(cam_f, resolution_hw, self.pad)
         Wp = cam_res[1]
         crop = self.pad // 2
-        o = crop - CNN_HALO if (mode == "fused" and apron == "minimal" and crop > CNN_HALO) else 0
+        o = crop - CNN_HALO if (mode in ("fused", "exact") and apron == "minimal" and crop > CNN_HALO) else 0
         # padded rows this band casts / owns for the sky sum / evaluates the field on
         p0 = 0 if row0 == 0 else row0 + o
         p1 = cam_res[0] if row1 == H else row1 + self.pad - o
@@ -851,7 +864,7 @@ class Renderer:
             sky_sum = sky_c[(own0 - p0) * Wp:(own1 - p0) * Wp].sum(dim=0, dtype=torch.float64)
         return dict(vid=vid, d2=d2, rd=rd, sky_c=sky_c, sky_sum=sky_sum, sky_cnt=(own1 - own0) * Wp, cast_rows=(p1 - p0), Wp=Wp,
                     rows=(e1 - e0), cols=Wp - 2 * o, first=(e0 - p0) * Wp + o, halo=crop - o,
-                    cam_ori=(torch.as_tensor(cam_ori, dtype=torch.float32) if mode == "fused"
+                    cam_ori=(torch.as_tensor(cam_ori, dtype=torch.float32) if mode in ("fused", "exact")
                              else torch.as_tensor(cam_ori, dtype=torch.float32).to(self.dev)), mode=mode)
 
     def band_finish(self, hd, sky_avg, num_samples, cnn_mode=None):
@@ -861,12 +874,14 @@ class Renderer:
             sky_avg = sky_avg.to(torch.float32).reshape(1, 64)
             full = hd["rows"] == hd["cast_rows"] and hd["cols"] == hd["Wp"]
             if mode == "fused" and self.field_falls_back():      # (the job-wide decision of dist.agree_precision)
-                mode, hd["cam_ori"] = "unfused", hd["cam_ori"].to(self.dev)
-            if mode == "fused":
+                mode = self.field_gate["path"]
+                if mode == "unfused":
+                    hd["cam_ori"] = hd["cam_ori"].to(self.dev)
+            if mode in ("fused", "exact"):
                 from . import fused
                 win = None if full else fused.Window(hd["cast_rows"] * hd["Wp"], hd["Wp"], hd["first"], hd["rows"], hd["cols"])
-                net_out = fused.field_fused(self, hd["vid"], hd["d2"], hd["rd"], hd["cam_ori"], hd["sky_c"], sky_avg,
-                                            num_samples, window=win)
+                field = fused.field_fused if mode == "fused" else fused.field_exact
+                net_out = field(self, hd["vid"], hd["d2"], hd["rd"], hd["cam_ori"], hd["sky_c"], sky_avg, num_samples, window=win)
             else:
                 vid, d2, rd, sky_c = hd["vid"], hd["d2"], hd["rd"], hd["sky_c"]
                 if not full:             # (a fused band that fell back: cut the evaluated window out of the cast block)
@@ -915,7 +930,9 @@ class Renderer:
             # host value for the fused path (its C entry points take host floats): a device copy here and the .cpu() that
             # would undo it are two host<->device synchronisations per frame, each draining the launch queue
             cam_ori = torch.as_tensor(pose[0], dtype=torch.float32)
-            if mode != "fused":
+            if mode not in ("fused", "exact", "unfused"):
+                raise ValueError(mode)
+            if mode == "unfused":
                 cam_ori = cam_ori.to(self.dev)
             if mode == "fused":
                 # per-style precision gates (once per style; a host synchronisation on the style's first frame) -- before the sky
@@ -923,7 +940,9 @@ class Renderer:
                 if getattr(self, "field_gate", None) is None and FIELD_GATE:
                     self.calibrate_style(pose, resolution_hw, num_samples)
                 if self.field_falls_back():      # this style / these weights are outside the fused path's tolerance: the fp32 op
-                    mode, cam_ori = "unfused", cam_ori.to(self.dev)       # sequence, all of it (sky MLP and CNN included)
+                    mode = self.field_gate["path"]       # sequence, all of it (sky MLP and CNN included), or with the field on the
+                    if mode == "unfused":                # fp32 MFMA kernel ("exact", Renderer.fallback)
+                        cam_ori = cam_ori.to(self.dev)
                     if cnn_mode is None:
                         cnn_mode = "torch"
             if mode == "fused":
@@ -945,6 +964,11 @@ class Renderer:
             elif mode == "fused":       # the whole padded frame, as a window too: its launch takes the 8 x 4-pixel ray blocks
                 from . import fused
                 window = fused.Window.crop(Hp, Wp, 0)
+            elif mode == "exact":       # no calibration, fp32 sky MLP and CNN as in "unfused"; the field kernel on the minimal apron
+                from . import fused     # (also with cnn=False: nothing in this kernel depends on which rays share a launch)
+                o = crop - CNN_HALO if (apron == "minimal" and crop > CNN_HALO) else 0
+                window = fused.Window.crop(Hp, Wp, o)
+                Hp, Wp, crop = Hp - 2 * o, Wp - 2 * o, crop - o
             if mode == "unfused":
                 outs = []
                 for r0 in range(0, R, ray_chunk):
@@ -956,7 +980,8 @@ class Renderer:
                 from . import fused
                 net_out = fused.field_fused(self, vid, d2, rd, cam_ori, sky_c, sky_avg, num_samples, window=window)
             else:
-                raise ValueError(mode)
+                from . import fused
+                net_out = fused.field_exact(self, vid, d2, rd, cam_ori, sky_c, sky_avg, num_samples, window=window)
             net_out = net_out.view(1, Hp, Wp, 64)
             ev.mark("field")
             if not cnn:
@@ -996,7 +1021,7 @@ def _render_frames(self, poses, resolution_hw=(540, 960), num_samples=24, mode="
         if getattr(self, "field_gate", None) is None and FIELD_GATE:
             self.calibrate_style(poses[0], resolution_hw, num_samples, more_poses=poses[len(poses) // 2:len(poses) // 2 + 1] if len(poses) > 2 else ())
         if self.field_falls_back():
-            mode = "unfused"
+            mode = self.field_gate["path"]       # "unfused" or "exact" (Renderer.fallback): every frame of the trajectory the same
     f0, c0, cam_res = frame_intrinsics(poses[0][3], resolution_hw, self.pad)
     crop = self.pad // 2
     o = crop - CNN_HALO if (apron == "minimal" and crop > CNN_HALO) else 0

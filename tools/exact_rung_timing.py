@@ -1,0 +1,147 @@
+#!/usr/bin/env python
+"""Times the fp32 field rung against the PyTorch fp32 op sequence it replaces, at the benchmark configuration (960x540, 24 samples,
+scene 2048, pose 0 of pattern 0, synthetic weights, style 8888), and writes profiles/exact_rung_timing.json.
+
+    python tools/exact_rung_timing.py [--reps 10] [--warmup 3] [--out profiles/exact_rung_timing.json]
+
+Two comparisons, each inside ONE process on one device (devices differ by up to 20 %):
+  field   fused.field_exact  vs  Renderer.field_unfused over the rays of the same (minimal-apron) window
+  frame   render_frame(mode="exact")  vs  render_frame(mode="unfused")
+Every figure is the median of `reps` HIP-event timings after `warmup` runs, the two sides interleaved; `faster` is true when the
+gain exceeds the spread (max - min) of either side.  The field kernel's time is also set against its matrix-issue floor: evaluated
+32-sample tiles x 5 888 MFMAs x 64 cycles / 1 024 SIMDs / the clock.
+Each comparison runs as a child process under its own `timeout`; the first failure ends the run (nothing more is started)."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HW, NS, SCENE = (540, 960), 24, 2048
+MFMA_PER_TILE_PASS, MFMA_CYCLES, SIMDS, CLOCK_GHZ = 5888, 64, 1024, 2.4     # the clock: the part's maximum, so the fraction is a lower bound
+STEP_TIMEOUT_S = {"field": 420, "frame": 420}
+
+
+def _setup():
+    import torch
+    sys.path.insert(0, ROOT)
+    from scenedreamer_amd import camera, synth
+    from scenedreamer_amd.renderer import Renderer
+    dev = torch.device("cuda:0")
+    scene = synth.make_scene(SCENE, 3407, device=dev)
+    R = Renderer(synth.make_weights(0), scene, dev)
+    R.set_style(synth.make_style(8888))
+    pose = camera.eval_camera_poses(scene, maxstep=40)[0]
+    return torch, R, pose
+
+
+def _time_pair(torch, a, b, reps, warmup):
+    """[ms] of a() and b(), interleaved, HIP events on the current stream."""
+    for _ in range(warmup):
+        a()
+        b()
+    torch.cuda.synchronize()
+    out = ([], [])
+    for _ in range(reps):
+        for fn, sink in ((a, out[0]), (b, out[1])):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            sink.append(e0.elapsed_time(e1))
+    return out
+
+
+def _summary(new, old):
+    s = lambda v: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v), spread_ms=max(v) - min(v), runs_ms=[round(x, 3) for x in v])
+    n, o = s(new), s(old)
+    gain = o["median_ms"] - n["median_ms"]
+    return n, o, dict(gain_ms=gain, speedup=o["median_ms"] / n["median_ms"], faster=bool(gain > max(n["spread_ms"], o["spread_ms"])))
+
+
+def step_field(reps, warmup):
+    torch, R, pose = _setup()
+    from scenedreamer_amd import fused
+    from scenedreamer_amd.renderer import CNN_HALO
+    with torch.no_grad():
+        vid, d2, rd, (Hp, Wp) = R.cast_rays(pose, HW)
+        n = Hp * Wp
+        vid, d2, rd = vid.view(n, R.M), d2.view(2, n, R.M), rd.view(n, 3)
+        sky_c = R.sky_features(rd)
+        sky_avg = sky_c.mean(dim=0, keepdim=True)
+        o = R.pad // 2 - CNN_HALO
+        win = fused.Window.crop(Hp, Wp, o)
+        rows, cols = Hp - 2 * o, Wp - 2 * o
+        cut = lambda t: t.view(Hp, Wp, -1)[o:o + rows, o:o + cols].reshape(rows * cols, -1).contiguous()
+        vid_w, rd_w, sky_w = cut(vid), cut(rd), cut(sky_c)
+        d2_w = torch.stack([cut(d2[0]), cut(d2[1])]).contiguous()
+        ori = torch.as_tensor(pose[0], dtype=torch.float32)
+        ori_dev = ori.to(R.dev)
+        chunk = 1 << 16
+
+        def exact():
+            return fused.field_exact(R, vid, d2, rd, ori, sky_c, sky_avg, NS, window=win)
+
+        def unfused():
+            return torch.cat([R.field_unfused(vid_w[r:r + chunk], d2_w[:, r:r + chunk], rd_w[r:r + chunk], ori_dev, sky_w[r:r + chunk],
+                                              sky_avg, NS) for r in range(0, rows * cols, chunk)])
+
+        diff = float((exact() - unfused()).abs().max())
+        new, old = _time_pair(torch, exact, unfused, reps, warmup)
+        hit = win.groups((vid_w[:, 0] != 0), ragged=True).any(dim=1)
+        tiles = int(hit.sum()) * 4 * (-(-NS // 4))
+    n_, o_, cmp_ = _summary(new, old)
+    floor_ms = tiles * MFMA_PER_TILE_PASS * MFMA_CYCLES / SIMDS / (CLOCK_GHZ * 1e6)
+    return dict(window=[rows, cols], rays=rows * cols, max_abs_diff_net_out=diff, field_exact=n_, field_unfused=o_, **cmp_,
+                evaluated_tile_passes=tiles, evaluated_samples=tiles * 32, matrix_floor_ms=floor_ms, clock_ghz_assumed=CLOCK_GHZ,
+                matrix_issue_fraction=floor_ms / n_["median_ms"])
+
+
+def step_frame(reps, warmup):
+    torch, R, pose = _setup()
+    exact = lambda: R.render_frame(pose, HW, NS, mode="exact")
+    unfused = lambda: R.render_frame(pose, HW, NS, mode="unfused")
+    diff = float((exact() - unfused()).abs().max())
+    new, old = _time_pair(torch, exact, unfused, reps, warmup)
+    n_, o_, cmp_ = _summary(new, old)
+    return dict(max_abs_diff_image=diff, render_frame_exact=n_, render_frame_unfused=o_, **cmp_,
+                frames_per_s_exact=1e3 / n_["median_ms"], frames_per_s_unfused=1e3 / o_["median_ms"])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "exact_rung_timing.json"))
+    ap.add_argument("--step", choices=["field", "frame"], help="(internal) run one comparison in this process and print its JSON")
+    args = ap.parse_args()
+    if args.step:
+        res = {"field": step_field, "frame": step_frame}[args.step](args.reps, args.warmup)
+        print("RESULT " + json.dumps(res))
+        return 0
+    if args.reps < 10 or args.warmup < 3:
+        print("note: the comparison is defined on >= 10 timings after >= 3 warm-up runs", file=sys.stderr)
+    rec = dict(config=dict(resolution_hw=list(HW), num_samples=NS, scene_size=SCENE, pose="pattern 0, pose 0 of maxstep 40", weights="synth.make_weights(0)",
+                           style=8888, reps=args.reps, warmup=args.warmup, timing="HIP events, sides interleaved, one process per comparison"))
+    for step in ("field", "frame"):
+        cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps),
+               "--warmup", str(args.warmup)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+        if r.returncode != 0 or not line:
+            print(f"step {step} failed with exit status {r.returncode}; nothing more is started\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}", file=sys.stderr)
+            return 1
+        rec[step] = json.loads(line[-1][len("RESULT "):])
+        print(step, json.dumps({k: v for k, v in rec[step].items() if not isinstance(v, dict)}), flush=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
