@@ -370,7 +370,9 @@ int sdn_conv_head(const float *x, const void *packed, const float *bias, void *o
  *   in_hi / in_lo: y as f16 planes (the layout of sdn_conv);  out_img dev f32 [3][H*W];  out_raw: NULL or dev f32 [3][H*W], conv4's
  *   output BEFORE tanh -- RenderCNN.forward's own return value (gancraft_base.py:221-225; _forward_global returns both, :598-603)
  *   packed: sdn_conv_chain_packed_weight_bytes() bytes from sdn_conv_chain_pack_weights (w4a, w4b dev f32 [256,256]; w4 dev f32 [3,256])
- *   consts dev f32 [sdn_conv_chain_consts_floats()]: conv4a.bias[256] | conv4b.bias[256] | conv4.bias padded with zeros to 64 */
+ *   consts dev f32 [sdn_conv_chain_consts_floats()]: conv4a.bias[256] | conv4b.bias[256] | conv4.bias padded with zeros to 64
+ *   The packed stream carries 2^sdn_field_trunk_shift() like the sky MLP's: max(|w4a|, 0.4 |w4b|, 0.4 |w4|) * 2^shift must stay
+ *   below 65504 (cnn.MfmaCNN checks it and uses the sdn_conv launches otherwise). */
 size_t sdn_conv_chain_packed_weight_bytes(void);
 size_t sdn_conv_chain_consts_floats(void);
 int sdn_conv_chain_pack_weights(const float *w4a, const float *w4b, const float *w4, void *packed, sdn_stream_t stream);
@@ -383,6 +385,9 @@ int sdn_conv_chain(const void *in_hi, const void *in_lo, const void *packed, con
  * w1 dev [256,33]; wh4_host host array of 4 dev pointers [256,256]; wc dev [64,256];
  * sky_partial dev f32 [sdn_sky_partial_rows(n_rays, n_workgroups), 64]: every wave's sum of its rays' sky_c (all rows are
  * written -- no float atomics, the mean is reproducible bit for bit).
+ * Every layer of the packed stream is stored times 2^sdn_field_trunk_shift() (sky_kernel takes the factor back out), so that the
+ * lo halves of the f16 split leave f16's subnormal range: the caller keeps max(|fc1.weight|, 0.4 |fc2..fc5, fc_out_c weight|) *
+ * 2^shift below f16's 65504 (fused.prepare_sky checks it).
  * sky_avg + counter (both or neither): dev f32 [64] and a dev uint32 that is ZERO before the first launch; the last
  * workgroup to finish adds the partial rows in row order (double accumulation) and writes the frame mean sum / n_rays,
  * then resets the counter.  Without them the caller adds the rows up. */

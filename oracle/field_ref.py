@@ -172,12 +172,16 @@ def volum_rendering_relu(sigma, dists, dim):
 # --------------------------------------------------------------------------- a-4, a-5, driver
 
 def forward_perpix(w, lut, voxel_dims, voxel_id, depth2, raydirs, cam_ori_t, z, global_enc, num_samples,
-                   sample_depth=3.0, dists_scale=0.25, sky_avg=None, dtype=torch.float32, return_aux=False):
+                   sample_depth=3.0, dists_scale=0.25, sky_avg=None, dtype=torch.float32, return_aux=False,
+                   feature_in=None, sky_c=None, volume_rendering=None):
     """Generator._forward_perpix + _forward_perpix_sub, scenedreamer.py:285-430, inference settings
     (deterministic sampling, keep_sky_out + keep_sky_out_avgpool + sky_global_avgpool, clip_feat_map=True).
 
     voxel_id [1,h,w,M,1] int32, depth2 [1,2,h,w,M,1], raydirs [1,h,w,1,3], cam_ori_t [1,3], z [1,256],
     global_enc [1,2]; lut = int64[680] minecraft id -> reduced label.  Returns net_out [1,h,w,64].
+    Given inputs for tests that isolate the arithmetic: feature_in [1,h,w,ns,128] replaces the hash-grid lookup, sky_c
+    [1,h,w,1,64] the sky MLP, volume_rendering(sigma, dists, dim) this module's volum_rendering_relu (whose `.float()`, the
+    reference's, keeps a float64 evaluation from being float64 throughout).
     """
     voxel_id = torch.as_tensor(voxel_id)
     depth2 = torch.as_tensor(depth2, dtype=torch.float32).clone()
@@ -203,13 +207,13 @@ def forward_perpix(w, lut, voxel_dims, voxel_id, depth2, raydirs, cam_ori_t, z, 
     ncoord = worldcoord2 / delim * 2 - 1               # :300
     genc = global_enc[:, None, None, None, :].repeat(1, ncoord.shape[1], ncoord.shape[2], ncoord.shape[3], 1)
     ncoord = torch.cat([ncoord, genc], dim=-1)         # :301-302
-    feature_in = grid_encoder(w, ncoord, dtype)        # :303
+    feature_in = grid_encoder(w, ncoord, dtype) if feature_in is None else torch.as_tensor(feature_in).to(dtype)   # :303
     net_out_s, net_out_c = render_mlp(w, feature_in, z, onehot.to(dtype), dtype)  # :305
 
     sky_in = positional_encoding(raydirs.expand(-1, -1, -1, 1, -1).contiguous(), 5, True)  # :368-369
-    skynet_out_c = sky_mlp(w, sky_in.to(dtype), z, dtype)                                  # :370
+    skynet_out_c = sky_mlp(w, sky_in.to(dtype), z, dtype) if sky_c is None else torch.as_tensor(sky_c).to(dtype)   # :370
 
-    weights = volum_rendering_relu(net_out_s, new_dists.to(dtype) * dists_scale, dim=-2)   # :373
+    weights = (volume_rendering or volum_rendering_relu)(net_out_s, new_dists.to(dtype) * dists_scale, dim=-2)   # :373
     weights = weights * torch.logical_not(sky_only_mask).to(dtype)                         # :376
     total_weights = torch.sum(weights, dim=-2, keepdim=True)
     is_gnd = (worldcoord2[..., [0]] <= 1.0).any(dim=-2, keepdim=True)                      # :380-381

@@ -75,6 +75,15 @@ class MfmaCNN:
         self.w4 = w["denoiser.conv4.weight"].reshape(3, 256).contiguous()
         self.b4 = w["denoiser.conv4.bias"].contiguous()
         self._planes = {}
+        if self.chain:      # the tail's packed stream carries 2^shift: weights it cannot hold go through conv_kernel launches instead
+            from . import fused
+            try:
+                fused.check_trunk_range(w["denoiser.conv4a.weight"], [w["denoiser.conv4b.weight"], w["denoiser.conv4.weight"]],
+                                        lib.sdn_field_trunk_shift(), "render CNN tail")
+            except fused.TrunkRangeError as e:
+                import warnings
+                warnings.warn(f"MfmaCNN: {e}; head and tail run as sdn_conv launches instead (no pre-tanh output)")
+                self.chain = False
         if self.chain:
             with torch.cuda.device(R.dev):
                 self.chain_packed = torch.empty(lib.sdn_conv_chain_packed_weight_bytes(), dtype=torch.uint8, device=R.dev)

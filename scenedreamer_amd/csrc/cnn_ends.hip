@@ -46,7 +46,7 @@ struct ChainParams {
 template <int T, int HS, int STAGE>
 __device__ __forceinline__ void act_stage_res(const f32x16 (&acc)[8], const ActIn &in, half8 (&bh)[16], half8 (&bl)[16],
                                               const half8 (&yh)[16], const half8 (&yl)[16], float &part, ActRegs &g) {
-    act_stage<T, HS, false, STAGE, true>(acc, in, bh, bl, part, g);
+    act_stage<T, HS, false, STAGE, true>(acc, in, bh, bl, part, g, TRUNK_K);   // (chain_pack_kernel: every layer times 2^TRUNK_SHIFT)
     if constexpr (STAGE == 1) {
 #pragma unroll
         for (int e = 0; e < 4; e++) g.y[e] += (float)yh[T][4 * HS + e] + (float)yl[T][4 * HS + e];
@@ -76,7 +76,7 @@ __device__ __forceinline__ void chain_b_unit(char *lds, Ring &r, LayerState &st,
     layer8_fetch<DBG, 16, true, false, false, U + 1, true>(bias, bias_pend, bias, h, st);
 #define SDN_STAGE(K) \
     if constexpr (U % UPS < PIECES / 4 && K < 4) ring_issue_piece<4 * (U % UPS) + ((K) & 3)>(lds, r); \
-    if constexpr (P::stage(K) >= 0 && P::PEND) act_stage<P::T, P::HS, false, P::stage(K) < 0 ? 0 : P::stage(K), true>(acc, in, bh, bl, part, st.g); \
+    if constexpr (P::stage(K) >= 0 && P::PEND) act_stage<P::T, P::HS, false, P::stage(K) < 0 ? 0 : P::stage(K), true>(acc, in, bh, bl, part, st.g, TRUNK_K); \
     if constexpr (P::stage(K) >= 0 && P::OWN) act_stage_res<P::T, P::HS, P::stage(K) < 0 ? 0 : P::stage(K)>(acc, in, bh, bl, yh, yl, part, st.g); \
     if constexpr (PF && K < 4) lds_frag<UN % UPS, (K) & 3>(r, pf_pos, nx[(K) & 3]); \
     __builtin_amdgcn_sched_barrier(0);
@@ -262,13 +262,14 @@ __global__ __launch_bounds__(256, 1) void chain_kernel(const ChainParams p) {
         for (int T = 0; T < 16; T++) { yh[T] = bh[T]; yl[T] = bl[T]; }
         float part = 0.f;
         // conv4a: its upper half is activated behind its own lower half, its lower half behind conv4b's head
-        layer8<DBG, 16, false, false, false>(lds, r, bh, bl, acc, cst + CC_B4A, cst + CC_B4A, cst, h, part);
+        layer8<DBG, 16, false, false, false>(lds, r, bh, bl, acc, cst + CC_B4A, cst + CC_B4A, cst, h, part, TRUNK_K, TRUNK_K);
         // conv4b (+ y): the same, every activation of ITS outputs with the residual
         chain_layer_b<DBG>(lds, r, bh, bl, acc, yh, yl, cst + CC_B4B, cst + CC_B4A, h, part);
         f32x16 col[2];
-        col[0] = bias_block<0>(cst + CC_B4, h);
-        col[1] = bias_block<1>(cst + CC_B4, h);
+        col[0] = zero16();
+        col[1] = zero16();
         chain_layer_out<DBG>(lds, r, bh, bl, acc, yh, yl, col, cst + CC_B4B, h, part, nxt.src, nh, nl);
+        out_descale(col, cst + CC_B4, h, TRUNK_K);
         asm volatile("" ::"v"(col[1]));   // (row block 1 of the projection is padding)
         // rows 0..2 of row block 0 = registers 0..2 of the h = 0 half: the image, gancraft_base.py:603
         if (cur.ok && h == 0) {

@@ -20,6 +20,8 @@ constexpr int MAX_LIN = 80;     // up to 78 samples per ray
 constexpr float ACT_SCALE = 0.4f; // LeakyReLU_0.2(x) = 0.4 * (1.5 x + |x|)
 // The packed weights of the trunk layers fc_1 .. fc_4 carry 2^TRUNK_SHIFT (pack_kernel has the reason); the MLP kernel takes
 // the factor back out of their accumulators in the activation's bias fma.  -DSDN_TRUNK_SHIFT=0 is the ablation build.
+// Every layer of the sky MLP (sky_pack_kernel) and of the render CNN's chained tail (chain_pack_kernel) carries it too: their
+// output layers descale in the bias fma behind layer_out (out_descale).
 #ifndef SDN_TRUNK_SHIFT
 #define SDN_TRUNK_SHIFT 8
 #endif
@@ -869,7 +871,8 @@ __device__ __forceinline__ void out_fetch(const float *bias_pend, int h, OutStat
 
 template <int DBG, int U>
 __device__ __forceinline__ void out_unit(char *lds, Ring &r, OutState &st, half8 (&bh)[16], half8 (&bl)[16],
-                                         const f32x16 (&acc)[8], f32x16 (&col)[2], const float *bias_pend, int h, float &part) {
+                                         const f32x16 (&acc)[8], f32x16 (&col)[2], const float *bias_pend, int h, float &part,
+                                         float k_pend) {
     constexpr int UNITS = 16, RD = RING_DEPTH, UPS = UNITS_PER_SLOT;
     if constexpr (U % UPS == 0 && U != 0) {
         st.pos_cur = ring_acquire<DBG>(lds, r);
@@ -890,8 +893,8 @@ __device__ __forceinline__ void out_unit(char *lds, Ring &r, OutState &st, half8
     out_fetch<DBG, U + 1>(bias_pend, h, st);
 #define SDN_STAGE(K) \
     if constexpr (U % UPS < PIECES / 4 && K < 4 && !(DBG & 1)) ring_issue_piece<4 * (U % UPS) + ((K) & 3)>(lds, r); \
-    if constexpr (ACT) act_stage<T, HS, false, K>(acc, in0, bh, bl, part, g0); \
-    if constexpr (TWO) act_stage<T, 1, false, K>(acc, in1, bh, bl, part, g1); \
+    if constexpr (ACT) act_stage<T, HS, false, K>(acc, in0, bh, bl, part, g0, k_pend); \
+    if constexpr (TWO) act_stage<T, 1, false, K>(acc, in1, bh, bl, part, g1, k_pend); \
     if constexpr (PF && K < 4) lds_frag<UN % UPS, (K) & 3>(r, pf_pos, nx[(K) & 3]); \
     __builtin_amdgcn_sched_barrier(0);
     col[0] = mfma16(a[0], bh[U], col[0]);
@@ -912,13 +915,14 @@ __device__ __forceinline__ void out_unit(char *lds, Ring &r, OutState &st, half8
 template <int DBG, int... Us>
 __device__ __forceinline__ void out_units(std::integer_sequence<int, Us...>, char *lds, Ring &r, OutState &st,
                                           half8 (&bh)[16], half8 (&bl)[16], const f32x16 (&acc)[8], f32x16 (&col)[2],
-                                          const float *bias_pend, int h, float &part) {
-    (out_unit<DBG, Us>(lds, r, st, bh, bl, acc, col, bias_pend, h, part), ...);
+                                          const float *bias_pend, int h, float &part, float k_pend) {
+    (out_unit<DBG, Us>(lds, r, st, bh, bl, acc, col, bias_pend, h, part, k_pend), ...);
 }
 
+// k_pend: the descale factor of the pending layer's accumulators (TRUNK_K when its packed weights carry 2^TRUNK_SHIFT)
 template <int DBG>
 __device__ __forceinline__ void layer_out(char *lds, Ring &r, half8 (&bh)[16], half8 (&bl)[16], const f32x16 (&acc)[8],
-                                          f32x16 (&col)[2], const float *bias_pend, int h, float &part) {
+                                          f32x16 (&col)[2], const float *bias_pend, int h, float &part, float k_pend = 1.f) {
     OutState st;
     ring_refresh_lane(lds, r);
     st.pos_cur = ring_acquire<DBG>(lds, r);
@@ -926,7 +930,17 @@ __device__ __forceinline__ void layer_out(char *lds, Ring &r, half8 (&bh)[16], h
     out_fetch<DBG, 0>(bias_pend, h, st);
     lds_unit<0>(r.lds_lane + st.pos_cur * SLOT_BYTES, st.ring[0]);
     lds_unit<1>(r.lds_lane + st.pos_cur * SLOT_BYTES, st.ring[1]);
-    out_units<DBG>(std::make_integer_sequence<int, 16>{}, lds, r, st, bh, bl, acc, col, bias_pend, h, part);
+    out_units<DBG>(std::make_integer_sequence<int, 16>{}, lds, r, st, bh, bl, acc, col, bias_pend, h, part, k_pend);
+}
+
+// col = bias + k * col for an output layer whose packed weights carry 1 / k and whose accumulators were seeded with zero
+__device__ __forceinline__ void out_descale(f32x16 (&col)[2], const float *bias, int h, float k) {
+    const f32x16 b0 = bias_block<0>(bias, h), b1 = bias_block<1>(bias, h);
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        col[0][e] = __builtin_fmaf(col[0][e], k, b0[e]);
+        col[1][e] = __builtin_fmaf(col[1][e], k, b1[e]);
+    }
 }
 
 // DBG & 512 (timing experiment, ablation builds): cycles of workgroup-thread 0 per segment of a pass, summed in LDS --

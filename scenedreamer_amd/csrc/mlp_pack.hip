@@ -190,7 +190,8 @@ __global__ __launch_bounds__(256) void sky_pack_kernel(const SkyPackParams p) {
     for (int e = 0; e < 8; e++) {
         const int k = layer == 0 ? kmap_first(s, h, e) : kmap_hidden(s, h, e);
         float v = 0.f;
-        if (k < K) v = W[(size_t)row * K + k] * (layer == 0 ? 1.0f : ACT_SCALE);
+        // every layer times 2^TRUNK_SHIFT (sky_kernel takes it back out): the lo halves leave f16's subnormal range
+        if (k < K) v = W[(size_t)row * K + k] * (layer == 0 ? 1.0f : ACT_SCALE) * (float)(1 << TRUNK_SHIFT);
         const _Float16 vh = (_Float16)v;
         hi[e] = vh;
         lo[e] = (_Float16)(v - (float)vh);
@@ -226,7 +227,8 @@ __global__ __launch_bounds__(256) void chain_pack_kernel(const ChainPackParams p
     for (int e = 0; e < 8; e++) {
         // conv4b / conv4 consume a' = LeakyReLU(x) / 0.4 (act_stage); conv4a consumes y itself
         const float w = (layer == 2 && row >= 3) ? 0.f : W[(size_t)row * HID + kmap_hidden(s, h, e)];
-        const float v = w * (layer == 0 ? 1.0f : ACT_SCALE);
+        // times 2^TRUNK_SHIFT like the sky MLP's stream (chain_kernel descales in its bias fmas)
+        const float v = w * (layer == 0 ? 1.0f : ACT_SCALE) * (float)(1 << TRUNK_SHIFT);
         const _Float16 vh = (_Float16)v;
         hi[e] = vh;
         lo[e] = (_Float16)(v - (float)vh);

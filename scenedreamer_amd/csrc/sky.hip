@@ -94,12 +94,16 @@ __global__ __launch_bounds__(256, 1) void sky_kernel(const SkyParams p) {
         const float *nul = cst;
         // fc1 (+ style term): 4 k-steps; fragments 0..2 of its upper half are activated behind its own lower half, the
         // remaining five (3..7) right after, the lower half behind fc2's head
-        layer8<DBG, 4, false, false, false>(lds, r, bh, bl, acc, cst + SC_BIAS1, cst + SC_BIAS1, nul, h, part);
-        act_step<3, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part);   // fragments 0..2 were activated inside the layer
-        act_step<4, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part);
-        act_step<5, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part);
-        act_step<6, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part);
-        act_step<7, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part);
+        // Every layer sky_pack_kernel packs carries 2^TRUNK_SHIFT (the lo halves of weights of magnitude ~0.03 would sit in f16's
+        // subnormal range otherwise: an error that is the same for every ray and so survives in the frame mean); tk takes it
+        // back out in the bias fma.  The fp6 image of fc2..fc5 (pack_mx_kernel) carries no shift.
+        constexpr float tk = TRUNK_K;
+        layer8<DBG, 4, false, false, false>(lds, r, bh, bl, acc, cst + SC_BIAS1, cst + SC_BIAS1, nul, h, part, tk, tk);
+        act_step<3, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part, tk);   // fragments 0..2 were activated inside the layer
+        act_step<4, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part, tk);
+        act_step<5, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part, tk);
+        act_step<6, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part, tk);
+        act_step<7, false>(acc, cst + SC_BIAS1, nul, h, bh, bl, part, tk);
         if constexpr (SMX) {
             // fc1's upper half (fragments 0..7 = K blocks 0, 1) was activated by the plain stages: block maxima from the
             // fragments, K block 0 converted here, K block 1 by fc2's first unit (the protocol of layer8x)
@@ -111,19 +115,21 @@ __global__ __launch_bounds__(256, 1) void sky_kernel(const SkyParams p) {
 #pragma unroll 1
             for (int l = 0; l < 4; l++) {
                 const float *bias = cst + SC_BIASH + l * HID, *bias_pend = l == 0 ? cst + SC_BIAS1 : cst + SC_BIASH + (l - 1) * HID;
-                if (l < 3) layer8x<DBG, 1, false, false>(lds, r, bh, bl, mx, acc, bias, bias_pend, nul, h, part);
+                if (l == 0) layer8x<DBG, 1, false, false>(lds, r, bh, bl, mx, acc, bias, bias_pend, nul, h, part, 1.f, tk);   // fc1's lower half is pending
+                else if (l < 3) layer8x<DBG, 1, false, false>(lds, r, bh, bl, mx, acc, bias, bias_pend, nul, h, part);
                 else layer8x<DBG, 2, false, false>(lds, r, bh, bl, mx, acc, bias, bias_pend, nul, h, part);
             }
         } else {
 #pragma unroll 1
             for (int l = 0; l < 4; l++)
                 layer8<DBG, 16, true, false, false>(lds, r, bh, bl, acc, cst + SC_BIASH + l * HID,
-                                                    l == 0 ? cst + SC_BIAS1 : cst + SC_BIASH + (l - 1) * HID, nul, h, part);
+                                                    l == 0 ? cst + SC_BIAS1 : cst + SC_BIASH + (l - 1) * HID, nul, h, part, tk, tk);
         }
         f32x16 col[2];
-        col[0] = bias_block<0>(cst + SC_BC, h);
-        col[1] = bias_block<1>(cst + SC_BC, h);
-        layer_out<DBG>(lds, r, bh, bl, acc, col, cst + SC_BIASH + 3 * HID, h, part);
+        col[0] = zero16();
+        col[1] = zero16();
+        layer_out<DBG>(lds, r, bh, bl, acc, col, cst + SC_BIASH + 3 * HID, h, part, SMX ? 1.f : tk);
+        out_descale(col, cst + SC_BC, h, tk);
         // ---- store sky_c[ray][feature] and accumulate the per-feature sum over rays -----------------------------
         if (ray_ok) {
 #pragma unroll

@@ -121,14 +121,16 @@ class TrunkRangeError(RuntimeError):
     propagate; the drop-in surfaces (modules.py, dropin.py) catch it and evaluate the call with the reference's own method."""
 
 
-def check_trunk_range(w1, trunk_hidden, shift):
+def check_trunk_range(w1, trunk_hidden, shift, what="field MLP trunk"):
     """The packed trunk weights (fc_1 .. fc_4) carry 2^shift (mlp_pack.hip pack_kernel): refuse a style whose weights would
-    leave f16's range there instead of rendering infinities.  One device->host read per style."""
+    leave f16's range there instead of rendering infinities.  One device->host read per style.  The same holds for every layer
+    of the sky MLP (sky_pack_kernel) and of the render CNN's chained tail (chain_pack_kernel): w1 = the layer that consumes
+    plain values, trunk_hidden = the ones that consume the 0.4-scaled activation."""
     tops = [float(w1.abs().max())] + [float(t.abs().max()) * 0.4 for t in trunk_hidden]
     m = max(tops) if all(math.isfinite(v) for v in tops) else float("nan")
     if not math.isfinite(m) or m * 2.0 ** shift >= TRUNK_F16_HEADROOM:
-        raise TrunkRangeError(f"field MLP trunk weights reach {m:.4g}: times 2^{shift} (the packed stream's scale) that leaves "
-                              f"f16's range; this style cannot be rendered by the MFMA field kernel")
+        raise TrunkRangeError(f"{what} weights reach {m:.4g}: times 2^{shift} (the packed stream's scale) that leaves "
+                              f"f16's range; they cannot be evaluated by this MFMA kernel")
     return m
 
 
@@ -541,6 +543,7 @@ def prepare_sky(R):
     w1 = w["sky_net.fc1.weight"].contiguous()
     wc = w["sky_net.fc_out_c.weight"].contiguous()
     packed_mx = torch.empty_like(packed)
+    check_trunk_range(w1, wh + [wc], lib.sdn_field_trunk_shift(), "sky MLP")     # every layer of the stream carries 2^shift
     with torch.cuda.device(R.dev):
         capi.check(lib.sdn_sky_pack_weights(w1.data_ptr(), ptrs, wc.data_ptr(), packed.data_ptr(), _stream(R.dev)))
         capi.check(lib.sdn_sky_pack_weights_mx(w1.data_ptr(), ptrs, wc.data_ptr(), packed_mx.data_ptr(), _stream(R.dev)))

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from conftest import golden
+from field_layout import decode_encode_buffers
 
 pytestmark = pytest.mark.gpu
 
@@ -87,14 +88,9 @@ def test_encode_matches_oracle(renderer, oracle, weights_full, lut, tag):
     torch.cuda.synchronize()
     _, aux = FR.forward_perpix(weights_full, lut, renderer.voxel_t.shape, g["voxel_id"], g["depth2"], g["raydirs"],
                                g["cam_ori"][None], g["z"], g["global_enc"], ns, sky_avg=g["sky_avg"], return_aux=True)
-    nch = (ns + 3) // 4
-    ntile = (R + 7) // 8
-    # the features are stored as the MLP's operands: per lane and k-step 8 f16 hi + 8 f16 lo (hi + lo = the value to 2^-22)
-    fh = buf["feat"].cpu().numpy().view(np.float16).reshape(ntile, nch, 8, 64, 2, 8).astype(np.float32)
-    feat = fh[..., 0, :] + fh[..., 1, :]
-    dist = buf["dist"].cpu().numpy().reshape(ntile, nch, 32)
-    label = buf["label"].cpu().numpy().reshape(ntile, nch, 32)
-    # un-permute: lane = h*32 + 4*ray_in_tile + sample_in_step ; level = 2*s + h
+    # the features are stored as the MLP's operands: per lane and k-step 8 f16 hi + 8 f16 lo (hi + lo = the value to 2^-22);
+    # the un-permutation (lane = h*32 + 4*ray_in_tile + sample_in_step ; level = 2*s + h) is tests/field_layout.py's
+    feat, dist, label = decode_encode_buffers(buf, R, ns)
     ref_feat = aux["feature_in"].numpy().reshape(R, ns, 16, 8)
     ref_dist = (aux["new_dists"].numpy().reshape(R, ns) * np.float32(0.25)).astype(np.float32)
     ref_idx = aux["new_idx"].numpy().reshape(R, ns)
@@ -102,18 +98,8 @@ def test_encode_matches_oracle(renderer, oracle, weights_full, lut, tag):
     red = lutt[g["voxel_id"].reshape(R, M)]
     red[red == 0] = 3
     ref_label = np.take_along_axis(red, ref_idx, axis=1)
-    got_feat = np.zeros_like(ref_feat)
-    got_dist = np.zeros_like(ref_dist)
-    got_label = np.zeros_like(ref_label)
-    for ray in range(R):
-        t, rt = divmod(ray, 8)
-        for smp in range(ns):
-            ch, si = divmod(smp, 4)
-            j = 4 * rt + si
-            got_dist[ray, smp] = dist[t, ch, j]
-            got_label[ray, smp] = label[t, ch, j]
-            for h in range(2):
-                got_feat[ray, smp, h::2] = feat[t, ch, :, h * 32 + j, :]
+    got_feat, got_dist, got_label = feat[:, :ns], dist[:, :ns], label[:, :ns]
+    assert got_feat.shape == ref_feat.shape and got_dist.shape == ref_dist.shape and got_label.shape == ref_label.shape
     np.testing.assert_array_equal(got_label, ref_label)
     np.testing.assert_array_equal(got_dist.view(np.int32), ref_dist.view(np.int32))
     # rays that hit nothing get weight 0 (scenedreamer.py:376); the kernel does not gather / write their features

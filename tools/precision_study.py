@@ -20,40 +20,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import field_ref as FR  # noqa: E402
-
-
-ROUND = {"x": "rtz", "w": "rtz"}     # how hi is rounded: rtz (v_cvt_pkrtz_f16_f32) or rtn (v_cvt_pk_f16_f32, gfx950)
-
-
-def split(x, mode="rtz"):
-    h = x.to(torch.float16)
-    if mode == "rtz":
-        over = h.float().abs() > x.abs()
-        hv = h.view(torch.int16)
-        hv = torch.where(over, hv - 1, hv)          # sign-magnitude: one step toward zero
-        h = hv.view(torch.float16)
-    hi = h.float()
-    lo = (x - hi).to(torch.float16).float()
-    return hi, lo
-
-
-def mm(x, W, terms):
-    """x [..., K], W [N, K] -> x W^T with the given subset of split terms ('f32' = exact)."""
-    if terms == "f32":
-        return x @ W.t()
-    xh, xl = split(x, ROUND["x"])
-    Wh, Wl = split(W, ROUND["w"])
-    y = xh @ Wh.t()
-    if "lh" in terms:
-        y = y + xh @ Wl.t()
-    if "hl" in terms:
-        y = y + xl @ Wh.t()
-    if "ll" in terms:
-        y = y + xl @ Wl.t()
-    return y
-
-
-T3, LH, HL, T1 = ("hh", "lh", "hl"), ("hh", "lh"), ("hh", "hl"), ("hh",)
+from oracle.split_ref import HL, LH, ROUND, T1, T3, mm, split  # noqa: E402
 
 
 def make_render_mlp(cfg):
