@@ -229,7 +229,7 @@ def forward_perpix(w, lut, voxel_dims, voxel_id, depth2, raydirs, cam_ori_t, z, 
     if return_aux:
         return net_out, dict(rand_depth=rand_depth, new_dists=new_dists, new_idx=new_idx, sigma=net_out_s,
                              color=net_out_c, sky=skynet_out_c, weights=weights, feature_in=feature_in,
-                             worldcoord2=worldcoord2)
+                             worldcoord2=worldcoord2, sky_only=sky_only_mask, nosky=nosky_mask.bool())
     return net_out
 
 

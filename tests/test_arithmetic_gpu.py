@@ -11,8 +11,6 @@ with T the fp64 truth from this repository's oracle on the CPU and E3 computed i
 summation-order allowance of tests/test_exact_rung_gpu.py): every single defect is at least 4 x outside it.  Every test prints
 kernel/E3 and kernel/E32; SDN_ARITH_RECORD=<file> collects them as JSON (profiles/split_arithmetic.json)."""
 import ctypes
-import json
-import os
 
 import numpy as np
 import pytest
@@ -22,39 +20,10 @@ import field_layout as FL
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4.0
-RECORD = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _record_file():
-    yield
-    path = os.environ.get("SDN_ARITH_RECORD")
-    if path:
-        with open(path, "w") as f:
-            json.dump(RECORD, f, indent=1, sort_keys=True)
-
-
-def _check(name, got, truth, emu, yard, factor=FACTOR, scale=None):
-    """max |got - T| <= factor x E3; prints and records kernel/E3 and kernel/E32.  scale: (E3, E32) measured elsewhere (a larger
-    frame of the same layer) where the case's own values are too few to be a yardstick.  E3 <= 8 x E32 is asserted here too: the
-    emulation runs on tensors the code under test folded, and a wrong fold must not move the kernel and its yardstick together."""
-    e = FL.max_err(got, truth)
-    e3, e32 = scale if scale is not None else (FL.max_err(emu, truth), FL.max_err(yard, truth))
-    RECORD[name] = dict(kernel=e, E3=e3, E32=e32, kernel_over_E3=e / e3, kernel_over_E32=e / e32)
-    if scale is not None:
-        RECORD[name]["yardstick_frame"] = "%dx%d" % FL.YARD_HW
-    print(f"{name:72s} kernel {e:.2e}  E3 {e3:.2e}  E32 {e32:.2e}  kernel/E3 {e / e3:5.2f}  kernel/E32 {e / e32:5.2f}")
-    assert e3 <= 8 * e32, (name, e3, e32)
-    assert e <= factor * e3, (name, e, e3)
-
-
-def _check_fp32(name, got, truth, yard, factor=FACTOR):
-    """An fp32 kernel: max |got - T| <= factor x E32, the error of the reference's own fp32 arithmetic."""
-    e, e32 = FL.max_err(got, truth), FL.max_err(yard, truth)
-    RECORD[name] = dict(kernel=e, E32=e32, kernel_over_E32=e / e32)
-    print(f"{name:72s} kernel {e:.2e}  E32 {e32:.2e}  kernel/E32 {e / e32:5.2f}")
-    assert e <= factor * e32, (name, e, e32)
+FACTOR = FL.FACTOR
+RECORD = FL.RECORD
+_record_file = FL.record_file_fixture()
+_check, _check_fp32 = FL.check, FL.check_fp32
 
 
 def _lossy(name, got, truth, yard):
@@ -76,14 +45,7 @@ def renderer(weights_full, scene256):
     return _renderer(weights_full, scene256)
 
 
-def _fold_from(R):
-    """The folded render-MLP constants the kernels were given (oracle/split_ref.py fold_render_mlp's layout), on the CPU."""
-    c = lambda t: t.detach().float().cpu()
-    w = R.w
-    return dict(w1=c(w["render_net.fc_1.weight"]), label_bias=c(R.label_bias), hidden=[c(R.mod[i][0]) for i in (2, 3, 4, 5, 6)],
-                beta=[c(R.mod[i][1]) for i in (2, 3, 4, 5, 6)], w_sigma=c(w["render_net.fc_sigma.weight"]).reshape(-1),
-                b_sigma=c(w["render_net.fc_sigma.bias"]).reshape(-1)[0], wc=c(w["render_net.fc_out_c.weight"]),
-                bc=c(w["render_net.fc_out_c.bias"]))
+_fold_from = FL.fold_from
 
 
 # ----------------------------------------------------------------------------------------------------- render MLP as an op
@@ -392,40 +354,12 @@ def _rays(R, scene):
 
 
 def _two_kernel_field(R, scene, ns):
-    """sdn_field_encode -> sdn_field_mlp (colour_terms = 3, term_eps = 0) on the small frame, and what the MLP kernel was given:
-    returns net_out [n,64] (GPU) and a dict of CPU tensors -- feat [n,ns,128], dist [n,ns], label [n,ns], sky_only / nosky [n],
-    sky_c [n,64], sky_avg [64] -- plus the ray arrays for the one-kernel forms."""
-    from scenedreamer_amd import fused
+    """FL.two_kernel_field on the small frame's rays."""
     pose, vid, d2, rd = _rays(R, scene)
-    n = vid.shape[0]
-    ori = torch.as_tensor(pose[0], dtype=torch.float32)
-    with torch.no_grad():
-        sky_c, sky_avg = fused.sky_fused(R, rd)
-        buf = fused.encode(R, vid, d2, rd, ori, ns)
-        net_out = fused.mlp_from(R, buf, sky_c, sky_avg.reshape(-1), n, ns)
-        torch.cuda.synchronize()
-    feat, dist, label = FL.decode_encode_buffers(buf, n, ns)
-    flags = buf["rayflag"].cpu().numpy()
-    sky_only = torch.from_numpy((flags & 1).astype(bool))
-    feat = torch.from_numpy(feat[:, :ns].reshape(n, ns, 128).copy())
-    feat[sky_only] = 0.0            # rays that hit nothing: the kernel gathers no features for them and gives them weight 0
-    given = dict(feat=feat, dist=torch.from_numpy(dist[:, :ns].copy()), label=torch.from_numpy(label[:, :ns].astype(np.int64)),
-                 sky_only=sky_only, nosky=torch.from_numpy(((flags >> 1) & 1).astype(bool)), sky_c=sky_c.cpu(), sky_avg=sky_avg.reshape(-1).cpu())
-    return net_out, given, (vid, d2, rd, ori, sky_c, sky_avg)
+    return FL.two_kernel_field(R, vid, d2, rd, torch.as_tensor(pose[0], dtype=torch.float32), ns)
 
 
-def _field_references(R, weights, given):
-    """fp64 truth, emulated 3-term MLP + fp32 compositing, fp32 MLP + fp32 compositing -- on exactly the values the kernel read."""
-    from oracle import split_ref as SR
-    n, ns = given["dist"].shape
-    x, lab = given["feat"].reshape(n * ns, 128), given["label"].reshape(-1)
-    z = R.z.cpu().numpy()
-    comp = lambda s, c, dt: SR.composite(s.reshape(n, ns), c.reshape(n, ns, 64), given["dist"].to(dt), given["sky_only"], given["nosky"],
-                                         given["sky_c"].to(dt), given["sky_avg"].to(dt))
-    truth = comp(*SR.render_mlp_ref(weights, x, z, lab, torch.float64), torch.float64)
-    yard = comp(*SR.render_mlp_ref(weights, x, z, lab, torch.float32), torch.float32)
-    emu = comp(*SR.render_mlp(_fold_from(R), x, lab), torch.float32)
-    return truth, emu, yard
+_field_references = FL.field_references
 
 
 @pytest.fixture(scope="module")
