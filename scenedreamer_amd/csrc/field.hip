@@ -41,15 +41,16 @@
 //                     accumulator / fragment-ring registers are dead.  No feature buffer, no 10.8 GB HBM round trip.
 //   sample_depth_kernel   mc_utils.sample_depth_batched as an op of its own.
 //   mfma_probe_kernel     checks the MFMA operand layouts the layer machinery relies on.
-// The encode stage's device functions (ray window, sample placement, collapsed-table gathers) are in field_enc.h, shared with
-// the fp32 field kernel (field_f32.hip).  The layer machinery (weight ring, activation stages, layers) is in mlp_layers.h, the weight packers (pack_kernel,
+// The encode stage's device functions (ray window, sample placement, collapsed-table gathers) are in field_enc.h, what a field
+// kernel does around its MLP (LDS prologue, volume rendering, sky compositing, launch helpers) in field_composite.h: both shared
+// with the fp32 field kernel (field_f32.hip).  The layer machinery (weight ring, activation stages, layers) is in mlp_layers.h, the weight packers (pack_kernel,
 // pack_mx_kernel) in mlp_pack.hip; the sky MLP (sky.hip) and the render CNN's 1x1 ends (cnn_ends.hip) run on them too.
 #include <hip/hip_fp16.h>
 
 #include <cstdlib>
 #include <utility>
 
-#include "field_enc.h"
+#include "field_composite.h"
 #include "mlp_layers.h"
 #include "sdn_common.h"
 
@@ -243,6 +244,137 @@ __global__ __launch_bounds__(256) void sample_depth_kernel(const SampleParams p)
 // =====================================================================================================
 // MLP + compositing (the structure of a pass and the layers: mlp_layers.h)
 // =====================================================================================================
+// ---- the input stage of a pass, a function per mode (MODE_RAW's few lines: in the kernel): the wave's 32 samples as B fragments bh / bl (fragment s of lane half h =
+// ---- features 16 s + 8 h .. + 7, split into f16 hi / lo), and this lane's sample's label and distance ---------------------------------
+// MODE_FUSED / _AUX: the encode stage of THIS pass (sample `sidx` of local ray rl = source ray rr), by this wave, into its own
+// B-fragment registers (the accumulators, the fragment ring and the fp6 state are dead here, so the gathers of several levels
+// can be in flight).  The loads are ordinary ones: hipcc's own vmcnt waits also retire the ring DMAs issued before them
+// (vector memory completes in order) -- a stricter wait than the ring's counted ones, never a wrong one.
+// gnd |= the sample lies at world x <= 1; depth = its rand_depth (the AUX kernel returns it)
+__device__ __forceinline__ void input_encode(const EncParams &enc, int rr, int rl, int sidx, bool ray_ok, bool use_feat, int h, half8 (&bh)[16],
+                                             half8 (&bl)[16], int &lab, float &dist, bool &gnd, float &depth) {
+    RayBoxes rb;
+    float dd[3];
+    enc_load_ray(enc, rr, rb, dd);
+    const EncSample es = enc_place(enc, rb, dd, rl, sidx, ray_ok);
+    gnd = gnd || es.gnd;
+    lab = es.label;
+    dist = es.dist;
+    depth = es.depth;
+    // 4 levels' gathers (64 x 16 B per lane) in flight at a time: two round trips per pass instead of eight
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+        float res[4][8];
+        enc_levels<4>(enc, es, 4 * b, h, use_feat, res);
+#pragma unroll
+        for (int t = 0; t < 4; t++) split8(res[t], bh[4 * b + t], bl[4 * b + t]);
+    }
+}
+
+// MODE_BUFFER: step tc of encode_kernel's feature buffer.  prefetched: input_prefetch(tc) was this wave's last prefetch -- the
+// step sits in a[190:255]; else (first pass of the kernel / after a skipped group) it is loaded here
+template <int DBG>
+__device__ __forceinline__ void input_buffer(const MlpParams &p, size_t tc, bool prefetched, bool tile_ok, int lane, int j, half8 (&bh)[16],
+                                             half8 (&bl)[16], int &lab, float &dist) {
+    float raw[8][8];
+    if (prefetched) {
+        if constexpr (DBG & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+#define SDN_PF_READ8(S, A0, A1, A2, A3, A4, A5, A6, A7) \
+    asm volatile("v_accvgpr_read_b32 %0, a" #A0 "\n\tv_accvgpr_read_b32 %1, a" #A1 "\n\tv_accvgpr_read_b32 %2, a" #A2 \
+                 "\n\tv_accvgpr_read_b32 %3, a" #A3 "\n\tv_accvgpr_read_b32 %4, a" #A4 "\n\tv_accvgpr_read_b32 %5, a" #A5 \
+                 "\n\tv_accvgpr_read_b32 %6, a" #A6 "\n\tv_accvgpr_read_b32 %7, a" #A7 \
+                 : "=v"(raw[S][0]), "=v"(raw[S][1]), "=v"(raw[S][2]), "=v"(raw[S][3]), "=v"(raw[S][4]), "=v"(raw[S][5]), \
+                   "=v"(raw[S][6]), "=v"(raw[S][7]))
+        SDN_PF_READ8(0, 190, 191, 192, 193, 194, 195, 196, 197);
+        SDN_PF_READ8(1, 198, 199, 200, 201, 202, 203, 204, 205);
+        SDN_PF_READ8(2, 206, 207, 208, 209, 210, 211, 212, 213);
+        SDN_PF_READ8(3, 214, 215, 216, 217, 218, 219, 220, 221);
+        SDN_PF_READ8(4, 222, 223, 224, 225, 226, 227, 228, 229);
+        SDN_PF_READ8(5, 230, 231, 232, 233, 234, 235, 236, 237);
+        SDN_PF_READ8(6, 238, 239, 240, 241, 242, 243, 244, 245);
+        SDN_PF_READ8(7, 246, 247, 248, 249, 250, 251, 252, 253);
+#undef SDN_PF_READ8
+        asm volatile("v_accvgpr_read_b32 %0, a254\n\tv_accvgpr_read_b32 %1, a255" : "=v"(lab), "=v"(dist));
+        if (!tile_ok) dist = 0.f;
+    } else {
+        // Inline asm as well, so that hipcc's wait insertion sees no vector-memory loads at all in the pass loop (with ordinary
+        // loads on this path it puts vmcnt(0) in front of the AGPR reads of the other path: a full drain of the weight ring per pass)
+        f32x4 t[16];
+        const char *base = reinterpret_cast<const char *>(p.feat + (tc * 8 * 64 + lane) * 8);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const char *a = base + k * 4096;
+            asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:16\n\t"
+                         "global_load_dwordx4 %2, %4, off offset:2048\n\tglobal_load_dwordx4 %3, %4, off offset:2064"
+                         : "=&v"(t[4 * k]), "=&v"(t[4 * k + 1]), "=&v"(t[4 * k + 2]), "=&v"(t[4 * k + 3]) : "v"(a) : "memory");
+        }
+        asm volatile("global_load_ubyte %0, %2, off\n\tglobal_load_dword %1, %3, off"
+                     : "=&v"(lab), "=&v"(dist) : "v"(p.label + tc * 32 + j), "v"(p.dist + tc * 32 + j) : "memory");
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
+                       "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]),
+                       "+v"(lab), "+v"(dist)
+                     :: "memory");
+        if (!tile_ok) dist = 0.f;
+#pragma unroll
+        for (int s = 0; s < 8; s++)
+#pragma unroll
+            for (int e = 0; e < 8; e++) raw[s][e] = t[2 * s + (e >> 2)][e & 3];
+    }
+#pragma unroll
+    for (int s = 0; s < 8; s++) {   // encode_kernel wrote the fragment already split: dwords 0..3 = f16 hi, 4..7 = f16 lo
+        const u32x4v hw = {__builtin_bit_cast(unsigned int, raw[s][0]), __builtin_bit_cast(unsigned int, raw[s][1]),
+                           __builtin_bit_cast(unsigned int, raw[s][2]), __builtin_bit_cast(unsigned int, raw[s][3])};
+        const u32x4v lw = {__builtin_bit_cast(unsigned int, raw[s][4]), __builtin_bit_cast(unsigned int, raw[s][5]),
+                           __builtin_bit_cast(unsigned int, raw[s][6]), __builtin_bit_cast(unsigned int, raw[s][7])};
+        bh[s] = __builtin_bit_cast(half8, hw);
+        bl[s] = __builtin_bit_cast(half8, lw);
+    }
+}
+
+// input_buffer's partner: step tn of the feature buffer (+ label, dist) -> a[190:255], issued in front of the output layer
+__device__ __forceinline__ void input_prefetch(const MlpParams &p, long tn, int lane, int j) {
+    const char *base = reinterpret_cast<const char *>(p.feat + ((size_t)tn * 8 * 64 + lane) * 8);
+    // k-steps 2k, 2k+1 (2048 B apart), two 16-B halves each -> a[190+16k : 205+16k]
+#define SDN_PF_LOAD4(K, R0, R1, R2, R3) \
+    asm volatile("global_load_dwordx4 a[" #R0 ":" #R0 "+3], %0, off\n\tglobal_load_dwordx4 a[" #R1 ":" #R1 "+3], %0, off offset:16\n\t" \
+                 "global_load_dwordx4 a[" #R2 ":" #R2 "+3], %0, off offset:2048\n\tglobal_load_dwordx4 a[" #R3 ":" #R3 "+3], %0, off offset:2064" \
+                 ::"v"(base + (K) * 4096) : "memory", SDN_PF_CLOBBERS)
+    // (the clobber list is what makes the kernel's register count include a[190:255])
+#define SDN_PF_CLOBBERS "a190", "a191", "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253"
+    SDN_PF_LOAD4(0, 190, 194, 198, 202);
+    SDN_PF_LOAD4(1, 206, 210, 214, 218);
+    SDN_PF_LOAD4(2, 222, 226, 230, 234);
+    SDN_PF_LOAD4(3, 238, 242, 246, 250);
+#undef SDN_PF_CLOBBERS
+#undef SDN_PF_LOAD4
+    asm volatile("global_load_ubyte a254, %0, off" ::"v"(p.label + (size_t)tn * 32 + j) : "memory", "a254");
+    asm volatile("global_load_dword a255, %0, off" ::"v"(p.dist + (size_t)tn * 32 + j) : "memory", "a255");
+}
+
+// ---- the workgroup's decision words (LDS_FLAGS at LDS address flags_a), accessed with explicit ds instructions: as a `volatile
+// int *` they became FLAT loads / stores (sc0 sc1) whose 64-bit addresses hipcc kept in scratch memory and each of which it followed
+// with s_waitcnt vmcnt(0) -- a complete drain of the weight ring's DMAs at every group start, after every pass (termination ballot)
+// and in every colour-skip decision (seen in the ISA of rounds 4-5: 17 flat operations, 48 of the kernel's 100 B of scratch) ----------
+__device__ __forceinline__ void flag_put(unsigned flags_a, int word, int v) {
+    asm volatile("ds_write_b32 %0, %1" ::"v"(flags_a + 4u * (unsigned)word), "v"(v) : "memory");
+}
+__device__ __forceinline__ i32x4v flag_get4(unsigned flags_a, int word0) {     // words word0 .. word0 + 3 (16-byte aligned), landed
+    i32x4v f;
+    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(f) : "v"(flags_a + 4u * (unsigned)word0) : "memory");
+    return f;
+}
+// One workgroup vote: every wave puts `mine` into word word0 + wave, a barrier, everybody reads the four words (the caller reduces
+// them, through readfirstlane, so that the decision is provably uniform).  The words may be rewritten only behind a barrier that
+// everybody passes after this read.
+__device__ __forceinline__ i32x4v workgroup_vote(unsigned flags_a, int word0, int lane, int wave, int mine) {
+    if (lane == 0) flag_put(flags_a, word0 + wave, mine);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    return flag_get4(flags_a, word0);
+}
+
 // CT = number of split terms of the colour layers fc_5 / fc_6 (3, or 2 = without the Whi.Xlo products)
 // FUSED = the encode stage runs inside this kernel (field_kernel): a pass's B fragments, distances and labels come from
 //         enc_place / enc_level instead of the feature buffer, the ray flags from the intersections themselves
@@ -264,24 +396,12 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
     const int q = j & 3;
 
     float *cst = reinterpret_cast<float *>(lds + LDS_CONST);
-    // the frame mean of the sky features arrives straight from sky_kernel (no host-side copy into the constant block).
-    // ONE writer per LDS word: two waves writing the same word without a barrier in between land in either order.
-    static_assert(C_SKY_AVG + OUTC == C_TOTAL, "sky_avg is the tail of the constant block");
-    for (int i = threadIdx.x; i < C_TOTAL; i += 256)
-        cst[i] = (p.sky_avg && i >= C_SKY_AVG) ? p.sky_avg[i - C_SKY_AVG] : p.consts[i];
+    stage_consts(cst, p.consts, p.sky_avg);
     // FUSED: the encode stage reads its tables from LDS (a copy of the parameter block with the three pointers redirected)
     EncParams enc = p.enc;
-    if constexpr (FUSED) {
-        float *e_scales = reinterpret_cast<float *>(lds + LDS_ENC_SCALES), *e_lin = reinterpret_cast<float *>(lds + LDS_ENC_LIN);
-        uint8_t *e_lut = reinterpret_cast<uint8_t *>(lds + LDS_ENC_LUT);
-        if (threadIdx.x < NLEV) e_scales[threadIdx.x] = p.enc.scales[threadIdx.x];
-        if (threadIdx.x < p.enc.ns + 1) e_lin[threadIdx.x] = p.enc.lin[threadIdx.x];
-        for (int i = threadIdx.x; i < 1024; i += 256) e_lut[i] = p.enc.lut[i];
-        enc.scales = e_scales; enc.lin = e_lin; enc.lut = e_lut;
-        if (p.cam_ori_dev) {   // (uniform: three scalar loads)
-            enc.ori[0] = p.cam_ori_dev[0]; enc.ori[1] = p.cam_ori_dev[1]; enc.ori[2] = p.cam_ori_dev[2];
-        }
-    }
+    if constexpr (FUSED)
+        stage_enc_tables(enc, p.enc, reinterpret_cast<float *>(lds + LDS_ENC_SCALES), reinterpret_cast<float *>(lds + LDS_ENC_LIN),
+                         reinterpret_cast<uint8_t *>(lds + LDS_ENC_LUT), p.cam_ori_dev);
     __syncthreads();
 
     Ring r;
@@ -326,17 +446,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
     // round 6: the result is then a loop-carried value, which hipcc copies into its carrier register right behind the
     // atomic, with the same wait; returning it into a reserved physical register is what the AGPR prefetch of the
     // two-kernel form does, and is not worth a second such contract here.)
-    // The workgroup's decision words (LDS_FLAGS), accessed with explicit ds instructions: as a `volatile int *` they became FLAT
-    // loads / stores (sc0 sc1) whose 64-bit addresses hipcc kept in scratch memory and each of which it followed with
-    // s_waitcnt vmcnt(0) -- a complete drain of the weight ring's DMAs at every group start, after every pass (termination
-    // ballot) and in every colour-skip decision (seen in the ISA of rounds 4-5: 17 flat operations, 48 of the kernel's 100 B of scratch).
-#define flags_a lds_addr(lds + LDS_FLAGS)
-    auto flag_put = [&](int word, int v) { asm volatile("ds_write_b32 %0, %1" ::"v"(flags_a + 4u * (unsigned)word), "v"(v) : "memory"); };
-    auto flag_get4 = [&](int word0) -> i32x4v {     // words word0 .. word0 + 3 (16-byte aligned), landed
-        i32x4v f;
-        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(f) : "v"(flags_a + 4u * (unsigned)word0) : "memory");
-        return f;
-    };
+    const unsigned flags_a = lds_addr(lds + LDS_FLAGS);   // the workgroup's decision words (workgroup_vote)
     int grp = blockIdx.x, grp_next = blockIdx.x + (int)gridDim.x;
     // FUSED: the first intersection of this lane's ray in group g (0 = none / no ray).  The next group's is loaded at the
     // START of the current one, so a group does not begin with an exposed round trip to memory
@@ -370,13 +480,10 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
         // (AUX also returns the per-sample sigma / colour of rays that hit nothing -- the reference evaluates them -- so it skips no group)
         const bool any_hit = AUX ? tile_ok : __any(!(flag & 1));
         // workgroup-uniform decisions: skip the group when none of its 32 rays hits anything; everybody learns the draw
-        if (lane == 0) flag_put(wave, any_hit ? 1 : 0);
-        if (threadIdx.x == 0) flag_put(4, drawn);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        if (threadIdx.x == 0) flag_put(flags_a, 4, drawn);
         // readfirstlane makes the decisions provably uniform: otherwise every loop-carried ring counter / pointer is
         // classified divergent, lives in VGPRs (spills!) and the DMA cannot use scalar addressing
-        const i32x4v fh = flag_get4(0), fd = flag_get4(4);
+        const i32x4v fh = workgroup_vote(flags_a, 0, lane, wave, any_hit ? 1 : 0), fd = flag_get4(flags_a, 4);
         const bool grp_hit = __builtin_amdgcn_readfirstlane(fh[0] | fh[1] | fh[2] | fh[3]) != 0;
         const int grp_next2 = __builtin_amdgcn_readfirstlane(fd[0]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -402,18 +509,17 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
                 for (int k = 0; k < 4; k++) mx.bm[k] = 0.f;
             }
             seg_tick<DBG>(lds, 9, t_seg);
-            const float *fin = p.feat + (tc * 8 * 64 + lane) * 8;
             unsigned long long t_in0 = 0;
             if constexpr (DBG & 128) t_in0 = __builtin_readcyclecounter();
             const long tc_s = (long)(tile_ok_s ? tile_s : 0) * p.nch + ch;    // tc as a scalar
+            // ---- input stage: this pass's B fragments (f16 hi / lo) and every sample's label and distance --------------------------
             int lab;
             float dist;
             float smp_depth = 0.f;   // AUX: this lane's sample depth
-            float raw[8][8];
-            // RAW: this lane's row of the [R, 128] feature matrix (clamped: lanes past the end evaluate the last row, store nothing)
+            // RAW: this lane's row of the [R, 128] feature matrix
             const long row = (long)(tile_ok ? tile : 0) * 256 + ch * 32 + j;
-            if constexpr (RAW) {
-                const long rc = row < p.R ? row : (long)p.R - 1;
+            if constexpr (RAW) {   // (inline: as a function of its own this loop costs mlp_kernel<0, 6, RAW> two VGPR spills)
+                const long rc = row < p.R ? row : (long)p.R - 1;   // clamped: lanes past the end evaluate the last row, store nothing
                 lab = p.label[rc];
                 dist = 0.f;
                 const float *src = p.feat + rc * FEAT + 8 * h;   // kmap_first: k-step s, lane half h = features 16 s + 8 h .. + 7
@@ -423,85 +529,10 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
                     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
                     split8(v, bh[s], bl[s]);
                 }
-            } else if constexpr (FUSED) {
-                // ---- the encode stage of THIS pass, by this wave, into its own B-fragment registers (the accumulators, the
-                //      fragment ring and the fp6 state are dead here, so the gathers of several levels can be in flight).
-                //      The loads are ordinary ones: hipcc's own vmcnt waits also retire the ring DMAs issued before them
-                //      (vector memory completes in order) -- a stricter wait than the ring's counted ones, never a wrong one.
-                RayBoxes rb;
-                float dd[3];
-                enc_load_ray(enc, rr, rb, dd);
-                const EncSample es = enc_place(enc, rb, dd, rl, ch * SAMP_PER_STEP + (j & 3), ray_ok);
-                gnd = gnd || es.gnd;
-                lab = es.label;
-                dist = es.dist;
-                if constexpr (AUX) smp_depth = es.depth;
-                const bool use_feat = AUX ? ray_ok : !(flag & 1);
-                // 4 levels' gathers (64 x 16 B per lane) in flight at a time: two round trips per pass instead of eight
-#pragma unroll
-                for (int b = 0; b < 2; b++) {
-                    float res[4][8];
-                    enc_levels<4>(enc, es, 4 * b, h, use_feat, res);
-#pragma unroll
-                    for (int t = 0; t < 4; t++) split8(res[t], bh[4 * b + t], bl[4 * b + t]);
-                }
-            } else {
-            if (pf_tc == tc_s && !(DBG & 256)) {
-                if constexpr (DBG & 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-#define SDN_PF_READ8(S, A0, A1, A2, A3, A4, A5, A6, A7) \
-    asm volatile("v_accvgpr_read_b32 %0, a" #A0 "\n\tv_accvgpr_read_b32 %1, a" #A1 "\n\tv_accvgpr_read_b32 %2, a" #A2 \
-                 "\n\tv_accvgpr_read_b32 %3, a" #A3 "\n\tv_accvgpr_read_b32 %4, a" #A4 "\n\tv_accvgpr_read_b32 %5, a" #A5 \
-                 "\n\tv_accvgpr_read_b32 %6, a" #A6 "\n\tv_accvgpr_read_b32 %7, a" #A7 \
-                 : "=v"(raw[S][0]), "=v"(raw[S][1]), "=v"(raw[S][2]), "=v"(raw[S][3]), "=v"(raw[S][4]), "=v"(raw[S][5]), \
-                   "=v"(raw[S][6]), "=v"(raw[S][7]))
-                SDN_PF_READ8(0, 190, 191, 192, 193, 194, 195, 196, 197);
-                SDN_PF_READ8(1, 198, 199, 200, 201, 202, 203, 204, 205);
-                SDN_PF_READ8(2, 206, 207, 208, 209, 210, 211, 212, 213);
-                SDN_PF_READ8(3, 214, 215, 216, 217, 218, 219, 220, 221);
-                SDN_PF_READ8(4, 222, 223, 224, 225, 226, 227, 228, 229);
-                SDN_PF_READ8(5, 230, 231, 232, 233, 234, 235, 236, 237);
-                SDN_PF_READ8(6, 238, 239, 240, 241, 242, 243, 244, 245);
-                SDN_PF_READ8(7, 246, 247, 248, 249, 250, 251, 252, 253);
-#undef SDN_PF_READ8
-                asm volatile("v_accvgpr_read_b32 %0, a254\n\tv_accvgpr_read_b32 %1, a255" : "=v"(lab), "=v"(dist));
-                if (!tile_ok) dist = 0.f;
-            } else {
-                // first pass of the kernel / after a skipped group: load here.  Inline asm as well, so that hipcc's wait
-                // insertion sees no vector-memory loads at all in this loop (with ordinary loads on this path it puts
-                // vmcnt(0) in front of the AGPR reads of the other path: a full drain of the weight ring per pass)
-                f32x4 t[16];
-                const char *base = reinterpret_cast<const char *>(fin);
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const char *a = base + k * 4096;
-                    asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:16\n\t"
-                                 "global_load_dwordx4 %2, %4, off offset:2048\n\tglobal_load_dwordx4 %3, %4, off offset:2064"
-                                 : "=&v"(t[4 * k]), "=&v"(t[4 * k + 1]), "=&v"(t[4 * k + 2]), "=&v"(t[4 * k + 3]) : "v"(a) : "memory");
-                }
-                asm volatile("global_load_ubyte %0, %2, off\n\tglobal_load_dword %1, %3, off"
-                             : "=&v"(lab), "=&v"(dist) : "v"(p.label + tc * 32 + j), "v"(p.dist + tc * 32 + j) : "memory");
-                asm volatile("s_waitcnt vmcnt(0)"
-                             : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
-                               "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]),
-                               "+v"(lab), "+v"(dist)
-                             :: "memory");
-                if (!tile_ok) dist = 0.f;
-#pragma unroll
-                for (int s = 0; s < 8; s++)
-#pragma unroll
-                    for (int e = 0; e < 8; e++) raw[s][e] = t[2 * s + (e >> 2)][e & 3];
             }
-#pragma unroll
-            for (int s = 0; s < 8; s++) {   // encode_kernel wrote the fragment already split: dwords 0..3 = f16 hi, 4..7 = f16 lo
-                const u32x4v hw = {__builtin_bit_cast(unsigned int, raw[s][0]), __builtin_bit_cast(unsigned int, raw[s][1]),
-                                   __builtin_bit_cast(unsigned int, raw[s][2]), __builtin_bit_cast(unsigned int, raw[s][3])};
-                const u32x4v lw = {__builtin_bit_cast(unsigned int, raw[s][4]), __builtin_bit_cast(unsigned int, raw[s][5]),
-                                   __builtin_bit_cast(unsigned int, raw[s][6]), __builtin_bit_cast(unsigned int, raw[s][7])};
-                bh[s] = __builtin_bit_cast(half8, hw);
-                bl[s] = __builtin_bit_cast(half8, lw);
-            }
-            }   // !FUSED
+            else if constexpr (FUSED)
+                input_encode(enc, rr, rl, ch * SAMP_PER_STEP + (j & 3), ray_ok, AUX ? ray_ok : !(flag & 1), h, bh, bl, lab, dist, gnd, smp_depth);
+            else input_buffer<DBG>(p, tc, pf_tc == tc_s && !(DBG & 256), tile_ok, lane, j, bh, bl, lab, dist);
             if constexpr (DBG & 128) {
                 asm volatile("s_waitcnt vmcnt(0)" ::"v"(bh[7]), "v"(bl[7]) : "memory");
                 t_stage += __builtin_readcyclecounter() - t_in0;
@@ -552,10 +583,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
                         const int wave_zero = __popcll(__ballot(zero_w));          // lanes: 2 per sample
                         // ONE barrier: flags[8..11] are written only here, and a wave reaches its next write only through the ring
                         // barriers of at least one whole layer, which nobody passes before having read these
-                        if (lane == 0) flag_put(8 + wave, wave_zero);
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        const i32x4v fz = flag_get4(8);
+                        const i32x4v fz = workgroup_vote(flags_a, 8, lane, wave, wave_zero);
                         const int grp_zero = __builtin_amdgcn_readfirstlane(fz[0] + fz[1] + fz[2] + fz[3]);
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         seg_tick<DBG>(lds, 11, t_seg);
@@ -600,22 +628,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
                 pf_tc = -1;
                 if (MODE == MODE_BUFFER && has_next && !(DBG & 256)) {
                     pf_tc = tn;
-                    const char *base = reinterpret_cast<const char *>(p.feat + ((size_t)tn * 8 * 64 + lane) * 8);
-                    // k-steps 2k, 2k+1 (2048 B apart), two 16-B halves each -> a[190+16k : 205+16k]
-#define SDN_PF_LOAD4(K, R0, R1, R2, R3) \
-    asm volatile("global_load_dwordx4 a[" #R0 ":" #R0 "+3], %0, off\n\tglobal_load_dwordx4 a[" #R1 ":" #R1 "+3], %0, off offset:16\n\t" \
-                 "global_load_dwordx4 a[" #R2 ":" #R2 "+3], %0, off offset:2048\n\tglobal_load_dwordx4 a[" #R3 ":" #R3 "+3], %0, off offset:2064" \
-                 ::"v"(base + (K) * 4096) : "memory", SDN_PF_CLOBBERS)
-                    // (the clobber list is what makes the kernel's register count include a[190:255])
-#define SDN_PF_CLOBBERS "a190", "a191", "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253"
-                    SDN_PF_LOAD4(0, 190, 194, 198, 202);
-                    SDN_PF_LOAD4(1, 206, 210, 214, 218);
-                    SDN_PF_LOAD4(2, 222, 226, 230, 234);
-                    SDN_PF_LOAD4(3, 238, 242, 246, 250);
-#undef SDN_PF_CLOBBERS
-#undef SDN_PF_LOAD4
-                    asm volatile("global_load_ubyte a254, %0, off" ::"v"(p.label + (size_t)tn * 32 + j) : "memory", "a254");
-                    asm volatile("global_load_dword a255, %0, off" ::"v"(p.dist + (size_t)tn * 32 + j) : "memory", "a255");
+                    input_prefetch(p, tn, lane, j);
                 }
             }
             f32x16 col[2];
@@ -627,28 +640,13 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
             if constexpr (RAW) {   // LightningMLP.forward's outputs for this lane's row: (sigma, c), layers.py:114, :124
                 if (tile_ok && row < p.R) {
                     if (h == 0) p.sigma_out[row] = sigma;
-#pragma unroll
-                    for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; g4++)   // registers 4 g4 .. 4 g4 + 3 of row block ib = features 32 ib + 8 g4 + 4 h + e
-                            *reinterpret_cast<float4 *>(p.net_out + (size_t)row * OUTC + 32 * ib + 8 * g4 + 4 * h) =
-                                make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
+                    store_colour_row(p.net_out + (size_t)row * OUTC, col, h);
                 }
                 n_done = ch + 1;
                 continue;
             }
-            // ---- volume rendering (mc_utils.py:154-161) over the 4 samples of each ray in this pass ---------------
-            const float fe = fmaxf(sigma, 0.f) * dist;
-            float incl = fe;
-            float up = quad_dpp<QUAD_UP1>(incl);
-            if (q >= 1) incl += up;
-            up = quad_dpp<QUAD_UP2>(incl);
-            if (q >= 2) incl += up;
-            float ex = quad_dpp<QUAD_UP1>(incl);
-            if (q == 0) ex = 0.f;
-            const float excl = carry + ex;
-            const float wgt = (1.f - __expf(-fe)) * __expf(-excl);
-            carry += quad_dpp<QUAD_LAST>(incl);
+            // ---- volume rendering + this pass's share of the ray's colour (field_composite.h) ----------------------
+            const float wgt = render_weight(sigma, dist, q, carry);
             tsum += wgt;
             if constexpr (AUX) {   // the per-sample return values of Generator._forward_perpix
                 const int sidx = ch * SAMP_PER_STEP + q;
@@ -659,26 +657,10 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
                         if (p.depth_out) p.depth_out[smp] = smp_depth;
                         if (p.sig_out) p.sig_out[smp] = sigma;
                     }
-                    if (p.col_out) {
-#pragma unroll
-                        for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                            for (int g4 = 0; g4 < 4; g4++)   // registers 4 g4 .. 4 g4 + 3 of row block ib = features 32 ib + 8 g4 + 4 h + e
-                                *reinterpret_cast<float4 *>(p.col_out + smp * OUTC + 32 * ib + 8 * g4 + 4 * h) =
-                                    make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
-                    }
+                    if (p.col_out) store_colour_row(p.col_out + smp * OUTC, col, h);
                 }
             }
-#pragma unroll
-            for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                for (int rr = 0; rr < 16; rr++) {
-                    const float rgb = fminf(fmaxf(col[ib][rr], -1.f), 1.f) + 1.f;  // scenedreamer.py:408
-                    float v = wgt * rgb;
-                    v += quad_dpp<QUAD_XOR1>(v);   // sum over the 4 samples of the ray held by this quad
-                    v += quad_dpp<QUAD_XOR2>(v);
-                    if ((rr >> 2) == q) outq[ib][rr & 3] += v;
-                }
+            accumulate_colour(col, wgt, q, outq);
             // ---- early ray termination (north star: wavefront ballots): once the transmittance exp(-carry) of EVERY ray of
             //      the workgroup's 32 is below eps, the remaining samples can change net_out by at most 2 eps (their weights
             //      sum to < eps and that mass goes to the sky term instead): skip the group's remaining passes.  The
@@ -692,10 +674,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
             if (p.term_depth > 0.f && ch + 1 < p.nch) {
                 const bool opaque = !ray_ok || (flag & 1) || carry > p.term_depth;
                 const bool wave_done = __all(opaque);
-                if (lane == 0) flag_put(wave, wave_done ? 1 : 0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                const i32x4v ft = flag_get4(0);
+                const i32x4v ft = workgroup_vote(flags_a, 0, lane, wave, wave_done ? 1 : 0);
                 const bool grp_done = __builtin_amdgcn_readfirstlane(ft[0] & ft[1] & ft[2] & ft[3]) != 0;
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -721,42 +700,14 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(const MlpParams p) {
 
         // ---- blend the sky, store ---------------------------------------------------------------------------------
         if constexpr (!RAW) {
-        tsum += quad_dpp<QUAD_XOR1>(tsum);
-        tsum += quad_dpp<QUAD_XOR2>(tsum);
-        if constexpr (FUSED) {   // nosky = the ray's last intersection is a voxel, or one of its samples lies at world x <= 1 (:335, :382)
-            int g = (int)gnd;
-            g |= quad_dpp<QUAD_XOR1>(g);
-            g |= quad_dpp<QUAD_XOR2>(g);
-            const bool last_hit = ray_ok && enc.voxel_id[(size_t)rr * enc.M + (enc.M - 1)] != 0;
-            if (last_hit || g) flag |= 2;
-        }
-        const bool sky_only = flag & 1, nosky = flag & 2;
-        if (sky_only) tsum = 0.f;  // scenedreamer.py:376
-        const float sky_w = 1.f - tsum;
-        if (ray_ok) {
-#pragma unroll
-            for (int ib = 0; ib < 2; ib++) {
-                const int f0 = 32 * ib + 8 * q + 4 * h;   // this lane owns features f0 .. f0+3 of its ray
-                const float4 sc = *reinterpret_cast<const float4 *>(p.sky_c + (size_t)p.win.src(ray) * OUTC + f0);
-                const float4 sa = *reinterpret_cast<const float4 *>(cst + C_SKY_AVG + f0);
-                const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, sav[4] = {sa.x, sa.y, sa.z, sa.w};
-                float o[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float sky = nosky ? (scv[e] * 0.f + sav[e]) : scv[e];          // :401, mask in {0,1}
-                    const float rgb_sky = fminf(fmaxf(sky, -1.f), 1.f) + 1.f;
-                    o[e] = (sky_only ? 0.f : outq[ib][e]) + sky_w * rgb_sky - 1.f;       // :410-413
-                    if constexpr (AUX) {
-                        if (p.skyb_out) p.skyb_out[(size_t)p.win.out_row(ray) * OUTC + f0 + e] = sky;
-                    }
-                }
-                if constexpr (AUX) {
-                    if (p.nosky_out && ib == 0 && q == 0 && h == 0) p.nosky_out[p.win.out_row(ray)] = nosky ? 1 : 0;
-                }
-                *reinterpret_cast<float4 *>(p.net_out + (size_t)p.win.out_row(ray) * OUTC + f0) = make_float4(o[0], o[1], o[2], o[3]);
+            if constexpr (FUSED) {   // nosky = the ray's last intersection is a voxel, or one of its samples lies at world x <= 1 (:335, :382)
+                const int g = quad_any(gnd);
+                const bool last_hit = ray_ok && enc.voxel_id[(size_t)rr * enc.M + (enc.M - 1)] != 0;
+                if (last_hit || g) flag |= 2;
             }
+            blend_sky_store<AUX>(cst, p.sky_c, p.net_out, p.win.src(ray), p.win.out_row(ray), ray_ok, tsum, flag, outq, q, h,
+                                 p.skyb_out, p.nosky_out);
         }
-        }   // !RAW
         grp = grp_next;
         grp_next = grp_next2;
         vox_cur = vox_nxt;
@@ -917,10 +868,6 @@ static int fill_mlp(MlpParams &p, const char *who, const void *packed, const flo
     if (!(term_eps >= 0.f && term_eps < 1.f)) return sdn::fail(SDN_ERR_INVALID, "%s: term_eps must be in [0, 1)", who);
     p.term_depth = term_eps > 0.f ? -logf(term_eps) : 0.f;
     p.passes = passes;
-    p.cam_ori_dev = nullptr; p.w_out = nullptr; p.depth_out = nullptr; p.sigma_out = nullptr;
-    p.sig_out = nullptr; p.col_out = nullptr; p.skyb_out = nullptr; p.nosky_out = nullptr;
-    p.colour_passes = nullptr; p.no_colour_skip = 0;
-    p.feat = nullptr; p.dist = nullptr; p.label = nullptr; p.rayflag = nullptr;
     p.wpk = (const half8 *)packed;
     p.consts = consts; p.sky_c = sky_c; p.net_out = net_out;
     p.sky_avg = sky_avg; p.ticket = ticket;
@@ -931,23 +878,17 @@ static int fill_mlp(MlpParams &p, const char *who, const void *packed, const flo
     return 0;
 }
 
-static int mlp_workgroups(const MlpParams &p, int32_t n_workgroups) {
-    int wg = n_workgroups > 0 ? n_workgroups : 256;
-    const int groups = sdn::div_up(p.n_tiles, 4);
-    return wg > groups ? groups : wg;
-}
-
 int sdn_field_mlp(const float *feat, const float *dist, const uint8_t *label, const uint8_t *rayflag, const void *packed,
                   const float *consts, const float *sky_c, float *net_out, int32_t n_rays, int32_t num_samples,
                   int32_t colour_terms, float term_eps, uint8_t *passes, int32_t n_workgroups, const int32_t *window_host,
                   const float *sky_avg, int32_t *ticket, sdn_stream_t stream) {
     SDN_REQUIRE(feat && dist && label && rayflag, "sdn_field_mlp: null pointer");
-    MlpParams p;
+    MlpParams p{};
     if (int rc = fill_mlp(p, "sdn_field_mlp", packed, consts, sky_c, net_out, n_rays, num_samples, colour_terms, term_eps, passes, window_host,
                           sky_avg, ticket))
         return rc;
     p.feat = feat; p.dist = dist; p.label = label; p.rayflag = rayflag;
-    const int wg = mlp_workgroups(p, n_workgroups);
+    const int wg = field_workgroups(p.n_tiles, n_workgroups);
     static const int dbg = [] {
         const char *e = getenv("SDN_MLP_DBG");   // timing experiments only; results are wrong unless 0
         return e ? atoi(e) : 0;
@@ -990,7 +931,7 @@ int sdn_field_render(const int32_t *voxel_id, const float *depth2, const float *
                      const float *sky_c, const float *sky_avg, float *net_out, int32_t colour_terms, float term_eps, uint8_t *passes,
                      int32_t n_workgroups, const int32_t *window_host, int32_t strat_division, int32_t *ticket, const float *cam_ori_dev,
                      const sdn_field_aux *aux, sdn_stream_t stream) {
-    MlpParams p;
+    MlpParams p{};
     const bool want_aux = aux && (aux->weights || aux->depth || aux->sigma || aux->colour || aux->sky_blended || aux->nosky);
     SDN_REQUIRE(!(want_aux && term_eps > 0.f), "sdn_field_render: the per-sample outputs need term_eps = 0 (every pass must run)");
     static const float zero3[3] = {0.f, 0.f, 0.f};
@@ -1019,7 +960,7 @@ int sdn_field_render(const int32_t *voxel_id, const float *depth2, const float *
         p.no_colour_skip = (aux->flags & SDN_FIELD_NO_COLOUR_SKIP) ? 1 : 0;
     }
     SDN_REQUIRE(colour_terms != 2, "sdn_field_render: colour_terms must be 3 or 6 (the 2-term profile exists for sdn_field_mlp only)");
-    const int wg = mlp_workgroups(p, n_workgroups);
+    const int wg = field_workgroups(p.n_tiles, n_workgroups);
 #ifdef SDN_MLP_ABLATION
     if (const char *e = getenv("SDN_MLP_DBG")) {   // timing experiments only
         if (atoi(e) == 512) { hipLaunchKernelGGL((mlp_kernel<512, 6, MODE_FUSED>), dim3(wg), dim3(256), 0, (hipStream_t)stream, p); return sdn::check_launch("sdn_field_render"); }
@@ -1041,19 +982,15 @@ int sdn_render_mlp(const float *x, const uint8_t *label, const void *packed, con
     SDN_REQUIRE(x && label && packed && consts && sigma && c, "sdn_render_mlp: null pointer");
     SDN_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 31), "sdn_render_mlp: n_rows must be in [1, 2^31)");
     SDN_REQUIRE(colour_terms == 3 || colour_terms == 6, "sdn_render_mlp: colour_terms must be 3 or 6");
-    MlpParams p;
-    p.feat = x; p.dist = nullptr; p.label = label; p.rayflag = nullptr;
-    p.wpk = (const half8 *)packed; p.consts = consts; p.sky_c = nullptr; p.net_out = c;
+    MlpParams p{};
+    p.feat = x; p.label = label;
+    p.wpk = (const half8 *)packed; p.consts = consts; p.net_out = c;
     p.R = (int32_t)n_rows; p.ns = 32; p.nch = 8;
     p.n_tiles = (int32_t)((n_rows + 255) / 256);
-    p.term_depth = 0.f; p.passes = nullptr;
-    p.win.n_src = p.R; p.win.pitch = 0; p.win.first = 0; p.win.cols = 0; p.win.ray0 = 0; p.win.tiled_bx = 0; p.win.rows = 0;
-    p.sky_avg = nullptr; p.ticket = ticket;
-    p.cam_ori_dev = nullptr; p.w_out = nullptr; p.depth_out = nullptr; p.sigma_out = sigma;
-    p.sig_out = nullptr; p.col_out = nullptr; p.skyb_out = nullptr; p.nosky_out = nullptr;
-    p.colour_passes = nullptr; p.no_colour_skip = 0;
-    p.enc = EncParams{};
-    const int wg = mlp_workgroups(p, n_workgroups);
+    p.win = raw_window(p.R);
+    p.ticket = ticket;
+    p.sigma_out = sigma;
+    const int wg = field_workgroups(p.n_tiles, n_workgroups);
     if (colour_terms == 6) hipLaunchKernelGGL((mlp_kernel<0, 6, MODE_RAW>), dim3(wg), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((mlp_kernel<0, 3, MODE_RAW>), dim3(wg), dim3(256), 0, (hipStream_t)stream, p);
     return sdn::check_launch("sdn_render_mlp");

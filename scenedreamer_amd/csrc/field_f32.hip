@@ -9,9 +9,9 @@
 //
 //   field_f32_kernel<FIELD>   per 32-sample tile (8 rays x 4 samples per wave, 4 waves = a 32-ray group per workgroup): the
 //                             encode stage of field_kernel (the same device functions, field_enc.h), fc_1 + label bias ->
-//                             fc_2 .. fc_4 -> fc_sigma, fc_5, fc_6, fc_out_c, then the compositing epilogue of mlp_kernel,
-//                             statement for statement.  Every sample of every ray that hits something is evaluated: no
-//                             early termination, no colour-branch skipping.
+//                             fc_2 .. fc_4 -> fc_sigma, fc_5, fc_6, fc_out_c, then the compositing epilogue mlp_kernel runs too
+//                             (field_composite.h: ONE definition of the volume rendering and the sky blend).  Every sample
+//                             of every ray that hits something is evaluated: no early termination, no colour-branch skipping.
 //   field_f32_kernel<RAW>     rows x [n,128] + label u8 [n] -> sigma [n], c [n,64].
 //   pack_f32_kernel           the folded weights in the order the kernel consumes them.
 //
@@ -25,9 +25,11 @@
 // Weights: 46 chunks of 32 KiB per pass (4 fc_1, 8 per hidden layer, 2 fc_out_c), the same for every pass.  The four waves
 // share one copy: chunk n + 1 is copied L2 -> LDS (global_load_lds, 16 B per lane, lane-linear image) into the second
 // buffer while chunk n is multiplied; one __syncthreads() per chunk (128 MFMAs of 64 cycles per wave) ends both.
+// What is not the MLP -- the LDS prologue, the (sigma, c) row store, volume rendering, sky compositing, the launch helpers -- is
+// field_composite.h, shared with field.hip; the kernel owns its LDS layout, its pass loop and the ray index it derives again for the epilogue.
 #include <type_traits>
 
-#include "field_enc.h"
+#include "field_composite.h"
 
 namespace {
 
@@ -134,21 +136,11 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
 
     chunk_fetch(p.wpk, wb0, 0, wave, lane16);
     float *cst = reinterpret_cast<float *>(lds + F32_LDS_CONST);
-    static_assert(C_SKY_AVG + OUTC == C_TOTAL, "sky_avg is the tail of the constant block");
-    for (int i = threadIdx.x; i < C_TOTAL; i += 256)
-        cst[i] = (p.sky_avg && i >= C_SKY_AVG) ? p.sky_avg[i - C_SKY_AVG] : p.consts[i];
+    stage_consts(cst, p.consts, p.sky_avg);
     EncParams enc = p.enc;
-    if constexpr (!RAW) {   // the encode stage reads its small tables from LDS, as in field_kernel
-        float *e_scales = reinterpret_cast<float *>(lds + F32_LDS_SCALES), *e_lin = reinterpret_cast<float *>(lds + F32_LDS_LIN);
-        uint8_t *e_lut = reinterpret_cast<uint8_t *>(lds + F32_LDS_LUT);
-        if (threadIdx.x < NLEV) e_scales[threadIdx.x] = p.enc.scales[threadIdx.x];
-        if (threadIdx.x < p.enc.ns + 1) e_lin[threadIdx.x] = p.enc.lin[threadIdx.x];
-        for (int i = threadIdx.x; i < 1024; i += 256) e_lut[i] = p.enc.lut[i];
-        enc.scales = e_scales; enc.lin = e_lin; enc.lut = e_lut;
-        if (p.cam_ori_dev) {
-            enc.ori[0] = p.cam_ori_dev[0]; enc.ori[1] = p.cam_ori_dev[1]; enc.ori[2] = p.cam_ori_dev[2];
-        }
-    }
+    if constexpr (!RAW)   // the encode stage reads its small tables from LDS, as in field_kernel
+        stage_enc_tables(enc, p.enc, reinterpret_cast<float *>(lds + F32_LDS_SCALES), reinterpret_cast<float *>(lds + F32_LDS_LIN),
+                         reinterpret_cast<uint8_t *>(lds + F32_LDS_LUT), p.cam_ori_dev);
     __syncthreads();   // chunk 0 and the tables are in place.  From here on: at a pass's start chunk 0 sits in buffer 0
 
     const int n_groups = (p.n_tiles + 3) >> 2;
@@ -277,76 +269,28 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
             if constexpr (RAW) {   // LightningMLP.forward's outputs for this lane's row: (sigma, c), layers.py:115, :125
                 if (tile_ok && row < p.R) {
                     if (h == 0) p.sigma_out[row] = sigma;
-#pragma unroll
-                    for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; g4++)
-                            *reinterpret_cast<float4 *>(p.net_out + (size_t)row * OUTC + 32 * ib + 8 * g4 + 4 * h) =
-                                make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
+                    store_colour_row(p.net_out + (size_t)row * OUTC, col, h);
                 }
                 continue;
             }
-            // ---- volume rendering (mc_utils.py:154-161) over the 4 samples of each ray in this pass: mlp_kernel's statements ----
-            const float fe = fmaxf(sigma, 0.f) * dist;
-            float incl = fe;
-            float up = quad_dpp<QUAD_UP1>(incl);
-            if (q >= 1) incl += up;
-            up = quad_dpp<QUAD_UP2>(incl);
-            if (q >= 2) incl += up;
-            float ex = quad_dpp<QUAD_UP1>(incl);
-            if (q == 0) ex = 0.f;
-            const float excl = carry + ex;
-            const float wgt = (1.f - __expf(-fe)) * __expf(-excl);
-            carry += quad_dpp<QUAD_LAST>(incl);
+            // ---- volume rendering + this pass's share of the ray's colour (field_composite.h) ------------------------------------
+            const float wgt = render_weight(sigma, dist, q, carry);
             tsum += wgt;
-#pragma unroll
-            for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const float rgb = fminf(fmaxf(col[ib][r], -1.f), 1.f) + 1.f;  // scenedreamer.py:408
-                    float v = wgt * rgb;
-                    v += quad_dpp<QUAD_XOR1>(v);   // sum over the 4 samples of the ray held by this quad
-                    v += quad_dpp<QUAD_XOR2>(v);
-                    if ((r >> 2) == q) outq[ib][r & 3] += v;
-                }
+            accumulate_colour(col, wgt, q, outq);
         }
 
-        // ---- blend the sky, store: mlp_kernel's statements --------------------------------------------------------------------
+        // ---- blend the sky, store --------------------------------------------------------------------------------------------
         if constexpr (!RAW) {
-            tsum += quad_dpp<QUAD_XOR1>(tsum);
-            tsum += quad_dpp<QUAD_XOR2>(tsum);
             // (the ray's addresses are derived again from an opaque copy of its index: computed at the group's start they would
             //  be carried through every pass, in scratch memory)
             int ray_e = rl;
             asm volatile("" : "+v"(ray_e));
             const int rr_e = enc.win.src(ray_e);
-            {   // nosky = the ray's last intersection is a voxel, or one of its samples lies at world x <= 1 (:335, :382)
-                int g = (int)gnd;
-                g |= quad_dpp<QUAD_XOR1>(g);
-                g |= quad_dpp<QUAD_XOR2>(g);
-                const bool last_hit = ray_ok && enc.voxel_id[(size_t)rr_e * enc.M + (enc.M - 1)] != 0;
-                if (last_hit || g) flag |= 2;
-            }
-            const bool sky_only = flag & 1, nosky = flag & 2;
-            if (sky_only) tsum = 0.f;  // scenedreamer.py:376
-            const float sky_w = 1.f - tsum;
-            if (ray_ok) {
-#pragma unroll
-                for (int ib = 0; ib < 2; ib++) {
-                    const int f0 = 32 * ib + 8 * q + 4 * h;   // this lane owns features f0 .. f0+3 of its ray
-                    const float4 sc = *reinterpret_cast<const float4 *>(p.sky_c + (size_t)rr_e * OUTC + f0);
-                    const float4 sa = *reinterpret_cast<const float4 *>(cst + C_SKY_AVG + f0);
-                    const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, sav[4] = {sa.x, sa.y, sa.z, sa.w};
-                    float o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float sky = nosky ? (scv[e] * 0.f + sav[e]) : scv[e];          // :401, mask in {0,1}
-                        const float rgb_sky = fminf(fmaxf(sky, -1.f), 1.f) + 1.f;
-                        o[e] = (sky_only ? 0.f : outq[ib][e]) + sky_w * rgb_sky - 1.f;       // :410-413
-                    }
-                    *reinterpret_cast<float4 *>(p.net_out + (size_t)p.win.out_row(ray_e) * OUTC + f0) = make_float4(o[0], o[1], o[2], o[3]);
-                }
-            }
+            // nosky = the ray's last intersection is a voxel, or one of its samples lies at world x <= 1 (:335, :382)
+            const int g = quad_any(gnd);
+            const bool last_hit = ray_ok && enc.voxel_id[(size_t)rr_e * enc.M + (enc.M - 1)] != 0;
+            if (last_hit || g) flag |= 2;
+            blend_sky_store<false>(cst, p.sky_c, p.net_out, rr_e, p.win.out_row(ray_e), ray_ok, tsum, flag, outq, q, h);
         }
     }
     __syncthreads();   // (a pass's last fetch -- chunk 0 for a pass that never came -- lands before the LDS is released)
@@ -400,12 +344,6 @@ int sdn_field_pack_weights_f32(const float *w1, const float *const *wh5_host, co
     return sdn::check_launch("sdn_field_pack_weights_f32");
 }
 
-static int f32_workgroups(const F32Params &p, int32_t n_workgroups) {
-    const int wg = n_workgroups > 0 ? n_workgroups : 256;
-    const int groups = sdn::div_up(p.n_tiles, 4);
-    return wg > groups ? groups : wg;
-}
-
 int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024, const float *table3,
                          uint32_t table_rows, const float *scales_dev, const float *genc_host, const float *cam_ori_host,
                          const float *voxel_dims_host, const float *lin_dev, const float *u_dev, int32_t n_rays, int32_t max_blocks,
@@ -416,7 +354,7 @@ int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const flo
     if (u_dev) return sdn::fail(SDN_ERR_UNSUPPORTED, "sdn_field_render_f32: deterministic sampling only (u_dev must be NULL)");
     static const float zero3[3] = {0.f, 0.f, 0.f};
     if (cam_ori_dev && !cam_ori_host) cam_ori_host = zero3;
-    F32Params p;
+    F32Params p{};
     if (int rc = fill_enc(p.enc, "sdn_field_render_f32", voxel_id, depth2, raydirs, lut1024, table3, table_rows, scales_dev, genc_host,
                           cam_ori_host, voxel_dims_host, lin_dev, nullptr, n_rays, max_blocks, num_samples, sample_depth, dists_scale, 0))
         return rc;
@@ -429,8 +367,7 @@ int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const flo
     p.n_tiles = p.enc.n_tiles = sdn::div_up(launch_rays, RAYS_PER_TILE);
     p.wpk = (const float *)packed; p.consts = consts; p.sky_c = sky_c; p.sky_avg = sky_avg; p.net_out = net_out;
     p.cam_ori_dev = cam_ori_dev;
-    p.x = nullptr; p.label = nullptr; p.sigma_out = nullptr;
-    hipLaunchKernelGGL((field_f32_kernel<F32_FIELD>), dim3(f32_workgroups(p, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((field_f32_kernel<F32_FIELD>), dim3(field_workgroups(p.n_tiles, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
     return sdn::check_launch("sdn_field_render_f32");
 }
 
@@ -438,15 +375,13 @@ int sdn_render_mlp_f32(const float *x, const uint8_t *label, const void *packed,
                        int64_t n_rows, int32_t n_workgroups, sdn_stream_t stream) {
     SDN_REQUIRE(x && label && packed && consts && sigma && c, "sdn_render_mlp_f32: null pointer");
     SDN_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 31), "sdn_render_mlp_f32: n_rows must be in [1, 2^31)");
-    F32Params p;
-    p.wpk = (const float *)packed; p.consts = consts; p.sky_c = nullptr; p.sky_avg = nullptr; p.net_out = c;
+    F32Params p{};
+    p.wpk = (const float *)packed; p.consts = consts; p.net_out = c;
     p.R = (int32_t)n_rows; p.ns = 32; p.nch = 8;
     p.n_tiles = (int32_t)((n_rows + 255) / 256);
-    p.win.n_src = p.R; p.win.pitch = 0; p.win.first = 0; p.win.cols = 0; p.win.ray0 = 0; p.win.tiled_bx = 0; p.win.rows = 0;
-    p.enc = EncParams{};
-    p.cam_ori_dev = nullptr;
+    p.win = raw_window(p.R);
     p.x = x; p.label = label; p.sigma_out = sigma;
-    hipLaunchKernelGGL((field_f32_kernel<F32_RAW>), dim3(f32_workgroups(p, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((field_f32_kernel<F32_RAW>), dim3(field_workgroups(p.n_tiles, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
     return sdn::check_launch("sdn_render_mlp_f32");
 }
 

@@ -134,6 +134,20 @@ def check_trunk_range(w1, trunk_hidden, shift, what="field MLP trunk"):
     return m
 
 
+def _const_block(R, n_floats, sigma_scale):
+    """The fp32 constant block of the field kernels (csrc/mlp_layers.h C_*): label bias, ModLinear biases, the density head
+    (its weights times sigma_scale), fc_out_c's bias; sky_avg, the tail, is filled per frame.  Returns (consts, offsets)."""
+    lib, w = _lib(), R.w
+    consts = torch.zeros(n_floats, dtype=torch.float32, device=R.dev)
+    off = [lib.sdn_field_const_offset(i) for i in range(6)]
+    consts[off[0]:off[0] + 12 * 256] = R.label_bias.reshape(-1)
+    consts[off[1]:off[1] + 5 * 256] = torch.stack([R.mod[i][1] for i in (2, 3, 4, 5, 6)]).reshape(-1)
+    consts[off[2]:off[2] + 256] = w["render_net.fc_sigma.weight"].reshape(-1) * sigma_scale   # (* 1.0 is exact)
+    consts[off[3]:off[3] + 64] = w["render_net.fc_out_c.bias"]
+    consts[off[4]] = w["render_net.fc_sigma.bias"].reshape(-1)[0]
+    return consts, off
+
+
 def prepare_style(R):
     """Pack the folded MLP weights into MFMA fragment order + build the fp32 constant block (once per style).  Two images
     of the stream: the 3-term f16 split everywhere, and the one with the colour layers as f16 + fp6 (colour_terms = 6)."""
@@ -152,14 +166,8 @@ def prepare_style(R):
         capi.check(rc, "sdn_field_pack_weights")
         rc = lib.sdn_field_pack_weights_mx(w1.data_ptr(), ptrs, wc.data_ptr(), packed_mx.data_ptr(), _stream(R.dev))
     capi.check(rc, "sdn_field_pack_weights_mx")
-    consts = torch.zeros(lib.sdn_field_consts_floats(), dtype=torch.float32, device=R.dev)
-    off = [lib.sdn_field_const_offset(i) for i in range(6)]
-    consts[off[0]:off[0] + 12 * 256] = R.label_bias.reshape(-1)
-    consts[off[1]:off[1] + 5 * 256] = torch.stack([R.mod[i][1] for i in (2, 3, 4, 5, 6)]).reshape(-1)
     # the MLP kernel's activations are LeakyReLU(x) / 0.4 (see mlp_layers.h act_stage): the density head absorbs the 0.4
-    consts[off[2]:off[2] + 256] = w["render_net.fc_sigma.weight"].reshape(-1) * 0.4
-    consts[off[3]:off[3] + 64] = w["render_net.fc_out_c.bias"]
-    consts[off[4]] = w["render_net.fc_sigma.bias"].reshape(-1)[0]
+    consts, off = _const_block(R, lib.sdn_field_consts_floats(), 0.4)
     R._fused_style = dict(packed=packed, packed_mx=packed_mx, consts=consts, sky_off=off[5], keep=wh, trunk_shift=shift)
     return R._fused_style
 
@@ -177,15 +185,38 @@ def prepare_style_f32(R):
     with torch.cuda.device(R.dev):
         capi.check(lib.sdn_field_pack_weights_f32(w1.data_ptr(), ptrs, wc.data_ptr(), packed.data_ptr(), _stream(R.dev)),
                    "sdn_field_pack_weights_f32")
-    consts = torch.zeros(lib.sdn_field_f32_consts_floats(), dtype=torch.float32, device=R.dev)
-    off = [lib.sdn_field_const_offset(i) for i in range(6)]
-    consts[off[0]:off[0] + 12 * 256] = R.label_bias.reshape(-1)
-    consts[off[1]:off[1] + 5 * 256] = torch.stack([R.mod[i][1] for i in (2, 3, 4, 5, 6)]).reshape(-1)
-    consts[off[2]:off[2] + 256] = w["render_net.fc_sigma.weight"].reshape(-1)      # unscaled: the activations are LeakyReLU itself
-    consts[off[3]:off[3] + 64] = w["render_net.fc_out_c.bias"]
-    consts[off[4]] = w["render_net.fc_sigma.bias"].reshape(-1)[0]
+    consts, _ = _const_block(R, lib.sdn_field_f32_consts_floats(), 1)     # unscaled: the activations are LeakyReLU itself
     R._fused_style_f32 = dict(packed=packed, consts=consts, keep=(wh, w1, wc))
     return R._fused_style_f32
+
+
+def _lin(R, ns, stratified=False):
+    """The stratified points' positions on the device, cached per renderer: deterministic linspace(0, 1, ns + 3)[1:-1]
+    (mc_utils.py:120), or the training-time sampling's linspace(0, 1, ns + 2)[:-1] (mc_utils.py:124)."""
+    buf = R.__dict__.setdefault("_fused_lin", {})
+    key = ("strat" if stratified else "det", ns)
+    lin = buf.get(key)
+    if lin is None:
+        lin = torch.linspace(0, 1, ns + 2)[:-1] if stratified else torch.linspace(0, 1, ns + 3)[1:-1]
+        lin = buf[key] = lin.contiguous().to(R.dev)
+    return lin
+
+
+def _cam_ori(R, cam_ori):
+    """(host f32 [3], device f32 [3] or None): a CUDA tensor is handed to the kernel as it is (no device -> host copy; the
+    host values are then unused zeros), anything else as host values."""
+    if isinstance(cam_ori, torch.Tensor) and cam_ori.is_cuda:
+        ori_dev = cam_ori.detach().reshape(-1).to(torch.float32).contiguous()
+        assert ori_dev.numel() == 3 and ori_dev.device == R.dev
+        return np.zeros(3, np.float32), ori_dev
+    return np.asarray(cam_ori.detach().cpu().numpy() if isinstance(cam_ori, torch.Tensor) else cam_ori, np.float32).reshape(3), None
+
+
+def _sky_avg(R, sky_avg):
+    """The frame mean of the sky features as a device f32 [64] (a host mean is accepted)."""
+    sky_avg = torch.as_tensor(sky_avg).reshape(-1).to(device=R.dev, dtype=torch.float32).contiguous()
+    assert sky_avg.numel() == 64
+    return sky_avg
 
 
 def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None):
@@ -203,20 +234,10 @@ def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None):
     for t, rows, what in ((vid, 0, "voxel_id"), (d2, 1, "depth2"), (rd, 0, "raydirs"), (sky_c, 0, "sky_c")):
         if not (t.is_cuda and t.device == R.dev and t.shape[rows] == window.n_src):
             raise ValueError(f"{what} must hold the window's {window.n_src} source rays on {R.dev}")
-    sky_avg = torch.as_tensor(sky_avg).reshape(-1).to(device=R.dev, dtype=torch.float32).contiguous()
-    assert sky_avg.numel() == 64
+    sky_avg = _sky_avg(R, sky_avg)
     net_out = torch.empty((n_rays, 64), dtype=torch.float32, device=R.dev)
-    buf = R.__dict__.setdefault("_fused_lin", {})
-    lin = buf.get(("det", ns))
-    if lin is None:
-        lin = buf[("det", ns)] = torch.linspace(0, 1, ns + 3)[1:-1].contiguous().to(R.dev)        # mc_utils.py:120
-    ori_dev = None
-    if isinstance(cam_ori, torch.Tensor) and cam_ori.is_cuda:
-        ori_dev = cam_ori.detach().reshape(-1).to(torch.float32).contiguous()
-        assert ori_dev.numel() == 3 and ori_dev.device == R.dev
-        ori = np.zeros(3, np.float32)
-    else:
-        ori = np.asarray(cam_ori.detach().cpu().numpy() if isinstance(cam_ori, torch.Tensor) else cam_ori, np.float32).reshape(3)
+    lin = _lin(R, ns)
+    ori, ori_dev = _cam_ori(R, cam_ori)
     with torch.cuda.device(R.dev):
         rc = _lib().sdn_field_render_f32(vid.data_ptr(), d2.data_ptr(), rd.data_ptr(), sc["lut"].data_ptr(), sc["table3"].data_ptr(),
                                          sc["T"], sc["scales"].data_ptr(), sc["genc"].ctypes.data, ori.ctypes.data,
@@ -413,29 +434,15 @@ def field_render(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, passes=None, u=Non
     if not isinstance(sky_c, int):
         sky_c = sky_c.contiguous()
     p_vid, p_d2, p_rd, p_sky = addr(vid, 0, "voxel_id"), addr(d2, 1, "depth2"), addr(rd, 0, "raydirs"), addr(sky_c, 0, "sky_c")
-    sky_avg = torch.as_tensor(sky_avg).reshape(-1).to(device=R.dev, dtype=torch.float32).contiguous()
-    assert sky_avg.numel() == 64
+    sky_avg = _sky_avg(R, sky_avg)
     if net_out is None:
         net_out = torch.empty((n_rays, 64), dtype=torch.float32, device=R.dev)
-    buf = R.__dict__.setdefault("_fused_lin", {})
-    if u is None:
-        lin = buf.get(("det", ns))
-        if lin is None:
-            lin = buf[("det", ns)] = torch.linspace(0, 1, ns + 3)[1:-1].contiguous().to(R.dev)        # mc_utils.py:120
-    else:
+    if u is not None:
         assert u.is_cuda and u.dtype == torch.float32 and tuple(u.shape) == (n_rays, ns + 1) and u.is_contiguous()
-        lin = buf.get(("strat", ns))
-        if lin is None:
-            lin = buf[("strat", ns)] = torch.linspace(0, 1, ns + 2)[:-1].contiguous().to(R.dev)      # mc_utils.py:124
+    lin = _lin(R, ns, stratified=u is not None)
     if "ticket" not in st:
         st["ticket"] = torch.zeros(2, dtype=torch.int32, device=R.dev)      # the kernel leaves it at zero
-    ori_dev = None
-    if isinstance(cam_ori, torch.Tensor) and cam_ori.is_cuda:
-        ori_dev = cam_ori.detach().reshape(-1).to(torch.float32).contiguous()
-        assert ori_dev.numel() == 3 and ori_dev.device == R.dev
-        ori = np.zeros(3, np.float32)
-    else:
-        ori = np.asarray(cam_ori.detach().cpu().numpy() if isinstance(cam_ori, torch.Tensor) else cam_ori, np.float32).reshape(3)
+    ori, ori_dev = _cam_ori(R, cam_ori)
     aux_c = None
     if aux is not None:
         shapes = {"weights": ((n_rays, ns), torch.float32), "depth": ((n_rays, ns), torch.float32), "sigma": ((n_rays, ns), torch.float32),
