@@ -354,6 +354,24 @@ int sdn_conv(const void *in_hi, const void *in_lo, int cin, int taps, int terms,
              void *out_hi, void *out_lo, float *out_f32, const float *proj_w, const float *proj_b, float *out_img, int H,
              int W, int n_workgroups, sdn_stream_t stream);
 
+/* The same convolutions in plain fp32 (csrc/cnn_f32.hip): RenderCNN.forward's F.conv2d calls (gancraft_base.py:206-219, zero
+ * padding 1 for the 3x3 layers) with every product an f32 x f32 fmaf on v_mfma_f32_32x32x2_f32 -- fp32's range (no restriction on
+ * the weights' magnitude), no precision form, nothing calibrated.  Supported (cin, taps): (256, 9), (256, 1), (64, 1); anything else
+ * returns SDN_ERR_UNSUPPORTED (sdn_conv_f32_packed_weight_bytes: 0).  Activations are plain f32 rows [H*W][channels], channels last,
+ * no planes and no border.  Summation order: per tap (ky, kx) one fmaf chain over the input channels from zero, the taps' partial
+ * sums added in f32 in tap order -- the same for every pixel, wherever it lies in the frame: a pixel's value depends on its 3x3
+ * neighbourhood only, bit for bit, not on H, W, its position or n_workgroups.
+ *   v   = LeakyReLU_0.2( (resid + (conv(in) + bias)) * (mod_w + 1) + mod_b )      each term optional, fp32, in this order
+ *   raw = proj_w . v + proj_b  (conv4, :221),  img = tanh(raw)  (:603)             optional; out_raw / out_img [3][H*W], either or both
+ * resid dev f32 rows [H*W][256]; it MAY be out_rows (the in-place residual update of conv2b / conv3b / conv4b).  out_rows may be
+ * NULL when a projection output is given.  For taps == 9 out_rows must not be in_rows (SDN_ERR_UNSUPPORTED). */
+size_t sdn_conv_f32_packed_weight_bytes(int cin, int taps);      /* = 256*cin*taps*4: every weight once */
+/* w_oihw dev f32 [256,cin,k,k] (k*k = taps) -> packed dev */
+int sdn_conv_pack_weights_f32(const float *w_oihw, int cin, int taps, void *packed, sdn_stream_t stream);
+int sdn_conv_f32(const float *in_rows, int cin, int taps, const void *packed, const float *bias, const float *resid,
+                 const float *mod_w, const float *mod_b, float *out_rows, const float *proj_w, const float *proj_b, float *out_img,
+                 float *out_raw, int H, int W, int n_workgroups, sdn_stream_t stream);
+
 /* The head of RenderCNN.forward as ONE kernel: y = LeakyReLU_0.2(conv1(x) + bias) (gancraft_base.py:206), x dev f32 rows
  * [H*W][64] (net_out), y as f16 hi / lo planes -- the same result as sdn_conv_planes_from_f32 -> sdn_conv(conv1) to f32
  * rounding, without the 64-channel planes in between.  w1 dev f32 [256,64]; bias dev f32 [256]; the output planes are

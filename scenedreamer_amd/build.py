@@ -36,6 +36,7 @@ SOURCES = {
     "cnn_ends.hip": MLP_FLAGS,
     "mlp_pack.hip": MLP_FLAGS,
     "cnn.hip": ABLATION,
+    "cnn_f32.hip": ["-fno-slp-vectorize"],
     "scene.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

@@ -32,6 +32,10 @@ def build_parser():
     ap.add_argument("--mode", default="fused", choices=["fused", "unfused", "exact"],
                     help="fused: MFMA kernels behind the per-style precision gates; unfused: the reference's fp32 op sequence on "
                          "PyTorch; exact: that sequence with the field on the fp32 MFMA kernel (no calibration, any weight range)")
+    ap.add_argument("--exact-cnn", dest="exact_cnn", default=None, choices=["torch", "f32"],
+                    help="render CNN of the exact path (--mode exact, or a closed gate with Renderer.fallback = 'exact'): torch = the "
+                         "reference's F.conv2d sequence (default; SDN_EXACT_CNN when not given); f32 = the fp32 MFMA kernel "
+                         "(fixed summation order, any weight range).  Every rank of a job must be given the same value")
     return ap
 
 
@@ -72,6 +76,8 @@ def main():
         scene, weights, style = sdist.broadcast_state(scene, weights, style, dev, src=0)
     R = Renderer(weights, scene, dev)
     R.set_style(style)
+    if args.exact_cnn is not None:
+        R.exact_cnn = args.exact_cnn
     poses = camera.eval_camera_poses(scene, maxstep=args.cam_maxstep, pattern=args.camera_mode, cam_ang=args.cam_ang)
     if world > 1 and args.mode == "fused":     # one decision of the render CNN's precision gate for all ranks
         sdist.agree_cnn_precision(R, poses[0], tuple(args.resolution_hw), args.num_samples)

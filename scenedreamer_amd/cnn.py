@@ -200,3 +200,93 @@ class MfmaCNN:
         self._conv(A, "conv4a", H, W, bias=bias("conv4a"), dst=B)
         self._conv(B, "conv4b", H, W, bias=bias("conv4b"), resid_planes=A, proj=(self.w4, self.b4), img=img)
         return img
+
+
+class F32CNN:
+    """The render CNN of the exact rung on the f32-input MFMA (csrc/cnn_f32.hip, sdn_conv_f32): RenderCNN.forward + tanh
+    (gancraft_base.py:202-225, :603) in plain fp32 -- weights of any range (no TrunkRangeError), no precision form, nothing
+    calibrated, and a fixed summation order: a pixel's value depends on its 9 x 9 neighbourhood of net_out only, bit for bit,
+    whatever the frame size, the band or the process.  Seven launches: conv1; conv2a; conv2b (+ residual, FiLM, in place); conv3a;
+    conv3b (likewise); conv4a; conv4b (+ residual, conv4 as its projection, tanh).  Activations travel as f32 rows [H*W][256]: two
+    buffers per frame size, A the running activation y, B the inner activation of each residual block."""
+
+    FLOP_PER_PIXEL = {"conv1": 2 * 64 * 256, "conv2a": 2 * 9 * 256 * 256, "conv2b": 2 * 9 * 256 * 256, "conv3a": 2 * 9 * 256 * 256,
+                      "conv3b": 2 * 9 * 256 * 256, "conv4a": 2 * 256 * 256, "conv4b (+ conv4)": 2 * (256 * 256 + 256 * 3)}    # sums to 5 015 040
+
+    def __init__(self, R):
+        self.R = R
+        self._planes = {}       # (H, W) -> the two row buffers; named as MfmaCNN's, so that the renderer's cache housekeeping covers both
+        lib = capi.lib()
+        w = R.w
+        self.packed = {}
+        with torch.cuda.device(R.dev):
+            for n, (cin, taps) in _LAYERS.items():
+                wt = w[f"denoiser.{n}.weight"]
+                assert tuple(wt.shape[:2]) == (256, cin) and wt.shape[2] * wt.shape[3] == taps, (n, tuple(wt.shape))
+                buf = torch.empty(lib.sdn_conv_f32_packed_weight_bytes(cin, taps), dtype=torch.uint8, device=R.dev)
+                capi.check(lib.sdn_conv_pack_weights_f32(wt.contiguous().data_ptr(), cin, taps, buf.data_ptr(), capi.current_stream(R.dev)),
+                           "sdn_conv_pack_weights_f32")
+                self.packed[n] = buf
+        self.bias = {n: (w[f"denoiser.{n}.bias"].contiguous() if f"denoiser.{n}.bias" in w else None) for n in _LAYERS}
+        self.w4 = w["denoiser.conv4.weight"].reshape(3, 256).contiguous()
+        self.b4 = w["denoiser.conv4.bias"].contiguous()
+
+    def _buffers(self, H, W):
+        key = (H, W)
+        if key not in self._planes:
+            mk = lambda: torch.empty(H * W * 256, dtype=torch.float32, device=self.R.dev)
+            while len(self._planes) >= 2:
+                self._planes.pop(next(iter(self._planes)))
+            self._planes[key] = (mk(), mk())
+        return self._planes[key]
+
+    _adapt = MfmaCNN._adapt
+
+    def conv(self, src, name, H, W, dst=None, bias=None, resid=None, mod=None, proj=None, img=None, raw=None):
+        """One sdn_conv_f32 launch with the weights of layer `name` (bias: a tensor, or None)."""
+        p = lambda t: t.data_ptr() if t is not None else None
+        cin, taps = _LAYERS[name]
+        with torch.cuda.device(self.R.dev):
+            capi.check(capi.lib().sdn_conv_f32(src.data_ptr(), cin, taps, self.packed[name].data_ptr(), p(bias), p(resid),
+                                               p(mod[0]) if mod else None, p(mod[1]) if mod else None, p(dst),
+                                               p(proj[0]) if proj else None, p(proj[1]) if proj else None, p(img), p(raw),
+                                               H, W, 0, capi.current_stream(self.R.dev)), "sdn_conv_f32")
+
+    def __call__(self, net_out, raw=None, timers=None):
+        """net_out [1,H,W,64] -> image [1,3,H,W] (tanh).  raw: optional f32 [1,3,H,W] that receives conv4's output before the tanh
+        (RenderCNN.forward's own return value, gancraft_base.py:221-225).  timers: optional dict; receives (start, end) event pairs
+        per launch, keyed like FLOP_PER_PIXEL."""
+        last = [None]
+
+        def tick(name=None):
+            if timers is None:
+                return
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            if name is not None:
+                timers.setdefault(name, []).append((last[0], e))
+            last[0] = e
+        _, H, W, _ = net_out.shape
+        A, B = self._buffers(H, W)
+        a = self._adapt()
+        b = self.bias
+        x = net_out.reshape(H * W, 64).contiguous()
+        img = torch.empty(1, 3, H, W, device=self.R.dev)
+        if raw is not None:
+            assert raw.is_contiguous() and raw.dtype == torch.float32 and tuple(raw.shape) == (1, 3, H, W), tuple(raw.shape)
+        tick()
+        self.conv(x, "conv1", H, W, dst=A, bias=b["conv1"])                                              # y = act(conv1(x))
+        tick("conv1")
+        self.conv(A, "conv2a", H, W, dst=B, bias=b["conv2a"])                                            # act(conv2a(y))
+        tick("conv2a")
+        self.conv(B, "conv2b", H, W, dst=A, bias=b["conv2b"], resid=A, mod=(a[0], a[1]))                 # y = act(mod(y + conv2b(.)))
+        tick("conv2b")
+        self.conv(A, "conv3a", H, W, dst=B, bias=b["conv3a"])
+        tick("conv3a")
+        self.conv(B, "conv3b", H, W, dst=A, bias=b["conv3b"], resid=A, mod=(a[2], a[3]))
+        tick("conv3b")
+        self.conv(A, "conv4a", H, W, dst=B, bias=b["conv4a"])
+        tick("conv4a")
+        self.conv(B, "conv4b", H, W, bias=b["conv4b"], resid=A, proj=(self.w4, self.b4), img=img, raw=raw)   # tanh(conv4(act(y + conv4b(.))))
+        tick("conv4b (+ conv4)")
+        return img

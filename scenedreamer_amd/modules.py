@@ -41,6 +41,7 @@ class Backend:
     in-place updates (load_state_dict, an optimizer step) and re-allocations (.cuda()) through the tensors' version counters
     and addresses, so packed weights are rebuilt exactly when they are stale."""
     mfma_cnn = Renderer.mfma_cnn
+    f32_cnn = Renderer.f32_cnn
     _cnn_form = Renderer._cnn_form
     _drop_other_cnn_planes = Renderer._drop_other_cnn_planes
     set_precision = Renderer.set_precision
@@ -293,7 +294,9 @@ class SKYMLPNative:
 
 
 class RenderCNNNative:
-    """forward(x [N,64,H,W], z [N,style]) -> conv4 output [N,3,H,W] (before tanh, like the reference)."""
+    """forward(x [N,64,H,W], z [N,style]) -> conv4 output [N,3,H,W] (before tanh, like the reference).
+    Opt-in `module.sdn_exact = True` (or SDN_CNN_EXACT=1): the call runs on the fp32 MFMA kernel (cnn.F32CNN, sdn_conv_f32) -- weights
+    of any range, no precision form chosen by a gate, a fixed summation order; at 1/16 of the f16 matrix rate."""
     _sdn_native = True
 
     def native_reason(self, x, z):
@@ -318,11 +321,12 @@ class RenderCNNNative:
         B.bind("denoiser.", self)
         n, _, H, W = x.shape
         raw = torch.empty((n, 3, H, W), dtype=torch.float32, device=x.device)
+        exact = bool(self.__dict__.get("sdn_exact", os.environ.get("SDN_CNN_EXACT", "0") not in ("0", "", "false")))
         with torch.no_grad():
             for i in range(n):
                 B.style("denoiser.", z, i, fold_denoiser)
                 net_out = x[i:i + 1].permute(0, 2, 3, 1).contiguous()      # channels-last rows [1,H,W,64]
-                B.mfma_cnn(net_out)(net_out, raw=raw[i:i + 1])
+                (B.f32_cnn() if exact else B.mfma_cnn(net_out))(net_out, raw=raw[i:i + 1])
         return raw
 
 

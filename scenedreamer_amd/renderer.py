@@ -88,6 +88,37 @@ class Renderer:
             raise ValueError(f"Renderer.fallback must be 'unfused' or 'exact', not {self.fallback!r}")
         return self.fallback
 
+    # The render CNN of the "exact" path (asked for directly, or adopted through fallback = "exact"): "torch" = render_cnn, the
+    # reference's F.conv2d sequence (default); "f32" = cnn.F32CNN, the fp32 MFMA kernel (csrc/cnn_f32.hip).  None = the environment
+    # variable SDN_EXACT_CNN, else "torch".  An explicit cnn_mode overrides it; "unfused" stays on PyTorch.  Like `fallback`, every
+    # rank of a distributed job must be given the same value: the two differ by fp32 rounding.
+    exact_cnn = None
+
+    def _exact_cnn_mode(self):
+        v = self.exact_cnn if self.exact_cnn is not None else os.environ.get("SDN_EXACT_CNN", "torch")
+        if v not in EXACT_CNN_MODES:
+            raise ValueError(f"Renderer.exact_cnn (or SDN_EXACT_CNN) must be 'torch' or 'f32', not {v!r}")
+        return v
+
+    def _resolve_cnn_mode(self, path, cnn_mode):
+        """Which render CNN runs on `path` (the path actually taken: "fused", "exact" or "unfused")."""
+        return resolve_cnn_mode(path, cnn_mode, self._exact_cnn_mode() if (cnn_mode is None and path == "exact") else "torch")
+
+    def f32_cnn(self):
+        """The fp32 MFMA render CNN (cnn.F32CNN), cached beside the f16 forms (the same events drop it)."""
+        cache = self.__dict__.setdefault("_mfma_cnns", {})
+        if "f32" not in cache:
+            from .cnn import F32CNN
+            cache["f32"] = F32CNN(self)
+        return cache["f32"]
+
+    def _run_cnn(self, cnn_mode, net_out):
+        if cnn_mode == "mfma":
+            return self.mfma_cnn(net_out)(net_out)
+        if cnn_mode == "f32":
+            return self.f32_cnn()(net_out)
+        return self.render_cnn(net_out)
+
     def __init__(self, weights, scene, device="cuda", num_blocks_early_stop=6, sample_depth=3.0, dists_scale=0.25,
                  pad=30):
         self.dev = torch.device(device)
@@ -892,12 +923,7 @@ class Renderer:
                 net_out = self.field_unfused(vid.contiguous(), d2.contiguous(), rd.contiguous(), hd["cam_ori"], sky_c.contiguous(), sky_avg,
                                              num_samples)
             net_out = net_out.view(1, hd["rows"], hd["cols"], 64)
-            if cnn_mode is None:
-                cnn_mode = "mfma" if mode == "fused" else "torch"
-            if cnn_mode == "mfma":
-                img = self.mfma_cnn(net_out)(net_out)
-            else:
-                img = self.render_cnn(net_out)
+            img = self._run_cnn(self._resolve_cnn_mode(mode, cnn_mode), net_out)
             p = hd["halo"]
             return img[:, :, p:-p, p:-p] if p else img
 
@@ -943,8 +969,7 @@ class Renderer:
                     mode = self.field_gate["path"]       # sequence, all of it (sky MLP and CNN included), or with the field on the
                     if mode == "unfused":                # fp32 MFMA kernel ("exact", Renderer.fallback)
                         cam_ori = cam_ori.to(self.dev)
-                    if cnn_mode is None:
-                        cnn_mode = "torch"
+            cnn_mode = self._resolve_cnn_mode(mode, cnn_mode)      # (validated before any work is done)
             if mode == "fused":
                 from . import fused
                 sky_c, sky_avg = fused.sky_fused(self, rd)
@@ -987,12 +1012,7 @@ class Renderer:
             if not cnn:
                 ev.done()
                 return net_out
-            if cnn_mode is None:
-                cnn_mode = "mfma" if mode == "fused" else "torch"
-            if cnn_mode == "mfma":
-                img = self.mfma_cnn(net_out)(net_out)
-            else:
-                img = self.render_cnn(net_out)
+            img = self._run_cnn(cnn_mode, net_out)
             if crop:
                 img = img[:, :, crop:-crop, crop:-crop]
             ev.mark("cnn")
@@ -1151,6 +1171,26 @@ def _render_frames(self, poses, resolution_hw=(540, 960), num_samples=24, mode="
 
 
 Renderer.render_frames = _render_frames
+
+EXACT_CNN_MODES = ("torch", "f32")
+CNN_MODES = ("mfma", "torch", "f32")
+
+
+def resolve_cnn_mode(path, cnn_mode=None, exact_cnn="torch"):
+    """Which render CNN runs: path = the path actually taken ("fused"; "exact" / "unfused", asked for or adopted by a closed gate
+    through Renderer.fallback), cnn_mode = the caller's explicit choice or None, exact_cnn = Renderer.exact_cnn resolved.
+    Returns "mfma" (cnn.MfmaCNN), "f32" (cnn.F32CNN) or "torch" (Renderer.render_cnn)."""
+    if path not in ("fused", "exact", "unfused"):
+        raise ValueError(path)
+    if exact_cnn not in EXACT_CNN_MODES:
+        raise ValueError(f"exact_cnn must be 'torch' or 'f32', not {exact_cnn!r}")
+    if cnn_mode is not None:
+        if cnn_mode not in CNN_MODES:
+            raise ValueError(f"cnn_mode must be one of {CNN_MODES} or None, not {cnn_mode!r}")
+        return cnn_mode
+    if path == "fused":
+        return "mfma"
+    return exact_cnn if path == "exact" else "torch"
 
 RECHECK_MIN_FRAMES = 2     # trajectories at least this long re-check the adopted CNN rung on their last frame (Renderer.recheck_cnn)
 FRONT_DEFAULT = "early"

@@ -2,11 +2,15 @@
 """Times the fp32 field rung against the PyTorch fp32 op sequence it replaces, at the benchmark configuration (960x540, 24 samples,
 scene 2048, pose 0 of pattern 0, synthetic weights, style 8888), and writes profiles/exact_rung_timing.json.
 
-    python tools/exact_rung_timing.py [--reps 10] [--warmup 3] [--out profiles/exact_rung_timing.json]
+    python tools/exact_rung_timing.py [--reps 10] [--warmup 3] [--out profiles/exact_rung_timing.json] [--only cnn]
 
-Two comparisons, each inside ONE process on one device (devices differ by up to 20 %):
+Three comparisons, each inside ONE process on one device (devices differ by up to 20 %):
   field   fused.field_exact  vs  Renderer.field_unfused over the rays of the same (minimal-apron) window
   frame   render_frame(mode="exact")  vs  render_frame(mode="unfused")
+  cnn     cnn.F32CNN (csrc/cnn_f32.hip)  vs  Renderer.render_cnn (PyTorch) on the same 548 x 968 net_out, and
+          render_frame(mode="exact") with exact_cnn = "f32" vs "torch"; the kernel's per-launch times, and its time against the
+          matrix-issue floor of the CNN: pixels x 5 015 040 FLOP / (1 024 SIMDs x 64 FLOP per clock x the clock)
+--only STEP runs one comparison and replaces only its key in an existing record.
 Every figure is the median of `reps` HIP-event timings after `warmup` runs, the two sides interleaved; `faster` is true when the
 gain exceeds the spread (max - min) of either side.  The field kernel's time is also set against its matrix-issue floor: evaluated
 32-sample tiles x 5 888 MFMAs x 64 cycles / 1 024 SIMDs / the clock.
@@ -21,7 +25,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HW, NS, SCENE = (540, 960), 24, 2048
 MFMA_PER_TILE_PASS, MFMA_CYCLES, SIMDS, CLOCK_GHZ = 5888, 64, 1024, 2.4     # the clock: the part's maximum, so the fraction is a lower bound
-STEP_TIMEOUT_S = {"field": 420, "frame": 420}
+STEP_TIMEOUT_S = {"field": 420, "frame": 420, "cnn": 420}
+CNN_FLOP_PER_PIXEL, F32_FLOP_PER_CLOCK_PER_SIMD = 5015040, 64
 
 
 def _setup():
@@ -111,22 +116,60 @@ def step_frame(reps, warmup):
                 frames_per_s_exact=1e3 / n_["median_ms"], frames_per_s_unfused=1e3 / o_["median_ms"])
 
 
+def step_cnn(reps, warmup):
+    torch, R, pose = _setup()
+    from scenedreamer_amd.cnn import F32CNN
+    with torch.no_grad():
+        net_out = R.render_frame(pose, HW, NS, mode="exact", cnn=False)          # [1, 548, 968, 64]: the minimal apron
+        _, Hc, Wc, _ = net_out.shape
+        k = R.f32_cnn()
+        new_fn, old_fn = (lambda: k(net_out)), (lambda: R.render_cnn(net_out))
+        diff = float((new_fn() - old_fn()).abs().max())
+        new, old = _time_pair(torch, new_fn, old_fn, reps, warmup)
+        timers = {}
+        for _ in range(reps):
+            k(net_out, timers=timers)
+        torch.cuda.synchronize()
+        launches = {}
+        for name, evs in timers.items():
+            ms = statistics.median(a.elapsed_time(b) for a, b in evs)
+            fl = F32CNN.FLOP_PER_PIXEL[name] * Hc * Wc
+            launches[name] = dict(median_ms=ms, gflop=fl / 1e9, tflops=fl / ms / 1e9,
+                                  matrix_floor_ms=fl / (SIMDS * F32_FLOP_PER_CLOCK_PER_SIMD * CLOCK_GHZ * 1e6))
+        n_, o_, cmp_ = _summary(new, old)
+        floor_ms = Hc * Wc * CNN_FLOP_PER_PIXEL / (SIMDS * F32_FLOP_PER_CLOCK_PER_SIMD * CLOCK_GHZ * 1e6)
+
+        def frame(which):
+            R.exact_cnn = which
+            return R.render_frame(pose, HW, NS, mode="exact")
+        fdiff = float((frame("f32") - frame("torch")).abs().max())
+        fnew, fold = _time_pair(torch, lambda: frame("f32"), lambda: frame("torch"), reps, warmup)
+        fn_, fo_, fcmp = _summary(fnew, fold)
+    return dict(net_out=[Hc, Wc], pixels=Hc * Wc, flop_per_pixel=CNN_FLOP_PER_PIXEL, max_abs_diff_image=diff, f32cnn=n_, render_cnn_torch=o_, **cmp_,
+                launches=launches, matrix_floor_ms=floor_ms, clock_ghz_assumed=CLOCK_GHZ, matrix_issue_fraction=floor_ms / n_["median_ms"],
+                frame=dict(max_abs_diff_image=fdiff, render_frame_exact_cnn_f32=fn_, render_frame_exact_cnn_torch=fo_, **fcmp))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "exact_rung_timing.json"))
-    ap.add_argument("--step", choices=["field", "frame"], help="(internal) run one comparison in this process and print its JSON")
+    ap.add_argument("--step", choices=["field", "frame", "cnn"], help="(internal) run one comparison in this process and print its JSON")
+    ap.add_argument("--only", choices=["field", "frame", "cnn"], help="run this comparison only; the other keys of an existing --out file are kept")
     args = ap.parse_args()
     if args.step:
-        res = {"field": step_field, "frame": step_frame}[args.step](args.reps, args.warmup)
+        res = {"field": step_field, "frame": step_frame, "cnn": step_cnn}[args.step](args.reps, args.warmup)
         print("RESULT " + json.dumps(res))
         return 0
     if args.reps < 10 or args.warmup < 3:
         print("note: the comparison is defined on >= 10 timings after >= 3 warm-up runs", file=sys.stderr)
     rec = dict(config=dict(resolution_hw=list(HW), num_samples=NS, scene_size=SCENE, pose="pattern 0, pose 0 of maxstep 40", weights="synth.make_weights(0)",
                            style=8888, reps=args.reps, warmup=args.warmup, timing="HIP events, sides interleaved, one process per comparison"))
-    for step in ("field", "frame"):
+    if args.only and os.path.exists(args.out):
+        with open(args.out) as f:
+            rec = {**json.load(f), "config": rec["config"]}
+    for step in ((args.only,) if args.only else ("field", "frame", "cnn")):
         cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps),
                "--warmup", str(args.warmup)]
         r = subprocess.run(cmd, capture_output=True, text=True)
