@@ -422,6 +422,27 @@ int sdn_sky_pack_weights_mx(const float *w1, const float *const *wh4_host, const
 int sdn_sky_mlp(const float *raydirs, const void *packed, const float *consts, float *sky_c, float *sky_partial, int32_t n_rays,
                 int32_t n_workgroups, float *sky_avg, uint32_t *counter, int32_t hidden_terms, int32_t encoded, sdn_stream_t stream);
 
+/* The sky MLP in plain fp32 (csrc/sky_f32.hip): the same call as sdn_sky_mlp -- SKYMLP.forward (imaginaire/generators/
+ * gancraft_base.py:150-169) on voxlib.positional_encoding(raydirs, 5, incl_orig) (positional_encoding_kernel.cu:40-75) and the
+ * frame mean of scenedreamer.py:592-598 -- with every product an f32 x f32 fmaf on v_mfma_f32_32x32x2_f32 (bit for bit a k-ordered
+ * fmaf chain).  The weights have fp32's range (no trunk shift: nothing to check before packing), and no bit of sky_c or sky_avg
+ * depends on the launch shape or on a library's summation order.  It is not more accurate than sdn_sky_mlp on weights that accepts.
+ *   w1 dev [256,33]; wh4_host host array of 4 dev pointers [256,256] (fc2 .. fc5); wc dev [64,256]; packed dev,
+ *   sdn_sky_f32_packed_weight_bytes() bytes (fc1 is stored padded to K = 64 with zeros).
+ *   consts: the layout and size of sdn_sky_consts_floats().
+ *   sky_partial dev f64 [sdn_sky_f32_partial_rows(n_rays, n_workgroups), 64]: every wave's sum of its rays' sky_c (a tile's 32
+ *   rays added in f32 as a depth-5 tree, everything after that in f64; all rows are written).
+ *   sky_avg + counter (both or neither): dev f32 [64] and a dev uint32 that is ZERO before the first launch; the last workgroup to
+ *   finish adds the partial rows in row order in f64, writes sky_avg = (float)(sum / n_rays) and resets the counter.
+ *   encoded: 0 = `raydirs` dev f32 [n_rays,3], encoded inside the kernel by sdn_posenc_fwd's own device function; 1 = dev f32
+ *   [n_rays,33], SKYMLP.forward's own argument.  On sdn_posenc_fwd's encoding both give the same bits.
+ *   n_workgroups <= 0: 256.  SDN_ERR_INVALID for null pointers, n_rays <= 0, sky_avg without counter or the reverse, another `encoded`. */
+size_t sdn_sky_f32_packed_weight_bytes(void);
+int sdn_sky_pack_weights_f32(const float *w1, const float *const *wh4_host, const float *wc, void *packed, sdn_stream_t stream);
+int32_t sdn_sky_f32_partial_rows(int32_t n_rays, int32_t n_workgroups);      /* rows of 64 doubles */
+int sdn_sky_mlp_f32(const float *raydirs, const void *packed, const float *consts, float *sky_c, double *sky_partial,
+                    int32_t n_rays, int32_t n_workgroups, float *sky_avg, uint32_t *counter, int32_t encoded, sdn_stream_t stream);
+
 /* test hook: C[32,32] = A[32,16] * B[16,32] through the MFMA operand layouts field.hip relies on */
 int sdn_debug_mfma_probe(const float *A, const float *B, float *C, sdn_stream_t stream);
 

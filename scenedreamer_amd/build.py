@@ -33,6 +33,7 @@ SOURCES = {
     "field.hip": MLP_FLAGS,
     "field_f32.hip": MLP_FLAGS,
     "sky.hip": MLP_FLAGS,
+    "sky_f32.hip": MLP_FLAGS,
     "cnn_ends.hip": MLP_FLAGS,
     "mlp_pack.hip": MLP_FLAGS,
     "cnn.hip": ABLATION,

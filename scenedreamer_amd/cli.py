@@ -36,6 +36,10 @@ def build_parser():
                     help="render CNN of the exact path (--mode exact, or a closed gate with Renderer.fallback = 'exact'): torch = the "
                          "reference's F.conv2d sequence (default; SDN_EXACT_CNN when not given); f32 = the fp32 MFMA kernel "
                          "(fixed summation order, any weight range).  Every rank of a job must be given the same value")
+    ap.add_argument("--exact-sky", dest="exact_sky", default=None, choices=["torch", "f32"],
+                    help="sky MLP of the exact path (--mode exact, or a closed gate with Renderer.fallback = 'exact'): torch = the "
+                         "reference's F.linear sequence and a library mean (default; SDN_EXACT_SKY when not given); f32 = the fp32 MFMA "
+                         "kernel (fixed summation order, any weight range).  Every rank of a job must be given the same value")
     return ap
 
 
@@ -78,6 +82,8 @@ def main():
     R.set_style(style)
     if args.exact_cnn is not None:
         R.exact_cnn = args.exact_cnn
+    if args.exact_sky is not None:
+        R.exact_sky = args.exact_sky
     poses = camera.eval_camera_poses(scene, maxstep=args.cam_maxstep, pattern=args.camera_mode, cam_ang=args.cam_ang)
     if world > 1 and args.mode == "fused":     # one decision of the render CNN's precision gate for all ranks
         sdist.agree_cnn_precision(R, poses[0], tuple(args.resolution_hw), args.num_samples)

@@ -26,15 +26,15 @@
 // share one copy: chunk n + 1 is copied L2 -> LDS (global_load_lds, 16 B per lane, lane-linear image) into the second
 // buffer while chunk n is multiplied; one __syncthreads() per chunk (128 MFMAs of 64 cycles per wave) ends both.
 // What is not the MLP -- the LDS prologue, the (sigma, c) row store, volume rendering, sky compositing, the launch helpers -- is
-// field_composite.h, shared with field.hip; the kernel owns its LDS layout, its pass loop and the ray index it derives again for the epilogue.
+// field_composite.h, shared with field.hip; the layer code (chunk_fetch, chunk_mul8, activate, chunk_out2) is mlp_f32.h, shared with
+// sky_f32.hip; the kernel owns its LDS layout, its pass loop and the ray index it derives again for the epilogue.
 #include <type_traits>
 
 #include "field_composite.h"
+#include "mlp_f32.h"
 
 namespace {
 
-constexpr int CHUNK_BYTES = 32768;
-constexpr int CHUNK_FLOATS = CHUNK_BYTES / 4;
 constexpr int N_CHUNKS = 4 + 5 * 8 + 2;     // fc_1 | fc_2 .. fc_6 | fc_out_c; even, so a chunk's buffer is its index & 1
 constexpr size_t PACKED_F32_FLOATS = (size_t)N_CHUNKS * CHUNK_FLOATS;
 static_assert(PACKED_F32_FLOATS == (size_t)HID * FEAT + 5 * HID * HID + OUTC * HID, "the stream holds every weight once");
@@ -61,65 +61,6 @@ struct F32Params {
     const uint8_t *label;      // RAW: [R]
     float *sigma_out;          // RAW: [R]
 };
-
-__device__ __forceinline__ float lrelu(float x) { return x > 0.f ? x : 0.2f * x; }   // F.leaky_relu(x, 0.2)
-
-__device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-template <int K>
-__device__ __forceinline__ void chunk_piece(const char *lane_src, char *dst) {
-    // the immediate offset (a 13-bit signed field: below 4096) is added to the global AND to the LDS address
-    __builtin_amdgcn_global_load_lds((glb_char *)(lane_src + (K / 4) * 4096), (lds_char *)(dst + (K / 4) * 4096), 16, (K % 4) * 1024, 0);
-}
-
-// this wave's quarter of chunk `cp` of the stream -> weight buffer cp & 1: 8 pieces of 1 KiB (64 lanes x 16 B).
-// The source address is a uniform base + this lane's 32-bit byte offset (the saddr form of the load): as 64-bit per-lane
-// pointers hipcc hoists the 8 addresses of every call out of the pass loop and keeps them in scratch memory.
-__device__ __forceinline__ void chunk_fetch(const float *wpk, char *wbuf, int cp, int wave, unsigned lane16) {
-    const char *src = reinterpret_cast<const char *>(wpk) + (size_t)cp * CHUNK_BYTES + wave * 8192;    // uniform
-    char *dst = wbuf + wave * 8192;      // wave-uniform; the DMA adds lane * 16
-    asm volatile("" : "+v"(lane16));
-    chunk_piece<0>(src + lane16, dst); chunk_piece<1>(src + lane16, dst); chunk_piece<2>(src + lane16, dst); chunk_piece<3>(src + lane16, dst);
-    chunk_piece<4>(src + lane16, dst); chunk_piece<5>(src + lane16, dst); chunk_piece<6>(src + lane16, dst); chunk_piece<7>(src + lane16, dst);
-}
-
-// acc[ib] (+)= sum over 16 k-steps of W_chunk[ib][k-step] x b[k-step]: one chunk of an 8-block layer.  A k-step's 2 KiB in the
-// chunk: [output blocks 0-3 | 4-7][lane][4 blocks], so a lane reads two float4 (conflict-free, lane-linear)
-__device__ __forceinline__ void chunk_mul8(const char *wbuf, int lane, const float (&b)[16], f32x16 (&acc)[8]) {
-    const float4 *w = reinterpret_cast<const float4 *>(wbuf) + lane;
-#pragma unroll
-    for (int kk = 0; kk < 16; kk++) {
-        const float4 a0 = w[kk * 128], a1 = w[kk * 128 + 64];
-        acc[0] = mfma_f32(a0.x, b[kk], acc[0]);
-        acc[1] = mfma_f32(a0.y, b[kk], acc[1]);
-        acc[2] = mfma_f32(a0.z, b[kk], acc[2]);
-        acc[3] = mfma_f32(a0.w, b[kk], acc[3]);
-        acc[4] = mfma_f32(a1.x, b[kk], acc[4]);
-        acc[5] = mfma_f32(a1.y, b[kk], acc[5]);
-        acc[6] = mfma_f32(a1.z, b[kk], acc[6]);
-        acc[7] = mfma_f32(a1.w, b[kk], acc[7]);
-    }
-}
-
-// act[ib][r] = LeakyReLU(acc[ib][r] + bias[channel]), acc = 0.  Registers 4 g .. 4 g + 3 of block ib = channels 32 ib + 8 g + 4 h + e
-__device__ __forceinline__ void activate(f32x16 (&acc)[8], const float *bias, int h, float (&act)[8][16]) {
-#pragma unroll
-    for (int ib = 0; ib < 8; ib++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const float4 bv = *reinterpret_cast<const float4 *>(bias + 32 * ib + 8 * g + 4 * h);
-            act[ib][4 * g + 0] = lrelu(acc[ib][4 * g + 0] + bv.x);
-            act[ib][4 * g + 1] = lrelu(acc[ib][4 * g + 1] + bv.y);
-            act[ib][4 * g + 2] = lrelu(acc[ib][4 * g + 2] + bv.z);
-            act[ib][4 * g + 3] = lrelu(acc[ib][4 * g + 3] + bv.w);
-        }
-#pragma unroll
-    for (int ib = 0; ib < 8; ib++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[ib][r] = 0.f;
-}
 
 template <int MODE>
 __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
@@ -246,18 +187,12 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
             f32x16 col[2];
             col[0] = zero16();
             col[1] = zero16();
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                chunk_fetch(p.wpk, c ? wb0 : wb1, c == 0 ? N_CHUNKS - 1 : 0, wave, lane16);   // (the last one: chunk 0 of the next pass)
-                const float2v *w = reinterpret_cast<const float2v *>(c ? wb1 : wb0) + lane;
-#pragma unroll
-                for (int kk = 0; kk < 64; kk++) {
-                    const float2v a = w[kk * 64];
-                    col[0] = mfma_f32(a[0], act[4 * c + (kk >> 4)][kk & 15], col[0]);
-                    col[1] = mfma_f32(a[1], act[4 * c + (kk >> 4)][kk & 15], col[1]);
-                }
-                __syncthreads();
-            }
+            chunk_fetch(p.wpk, wb1, N_CHUNKS - 1, wave, lane16);
+            chunk_out2<0>(wb0, lane, act, col);
+            __syncthreads();
+            chunk_fetch(p.wpk, wb0, 0, wave, lane16);   // (chunk 0 of the next pass)
+            chunk_out2<1>(wb1, lane, act, col);
+            __syncthreads();
 #pragma unroll
             for (int ib = 0; ib < 2; ib++)
 #pragma unroll
@@ -303,9 +238,6 @@ struct PackF32Params {
     const float *wc;      // [64,256]
     float *out;
 };
-
-// channel that accumulator register r of lane half h holds inside its 32-channel block = k of k-step r of that input block
-__host__ __device__ inline int kmap_f32(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
 
 __global__ __launch_bounds__(256) void pack_f32_kernel(const PackF32Params p) {
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;   // one thread per float of the stream

@@ -11,11 +11,10 @@
 // large, and packs 64/post entries per wave when post is tiny (the sky ray
 // directions have post = 3: a CUDA-style 16-wide x-tile would leave 13 of 16
 // lanes idle there).
+#include "posenc_enc.h"
 #include "sdn_common.h"
 
 namespace {
-
-constexpr float kPiF = 3.141592654f;  // CUDART_PI_F
 
 __global__ __launch_bounds__(256) void posenc_fwd_kernel(const float *__restrict__ in, float *__restrict__ out,
                                                          int64_t n, int64_t post, int ndeg, int incl_orig) {
@@ -25,9 +24,8 @@ __global__ __launch_bounds__(256) void posenc_fwd_kernel(const float *__restrict
         const float x = in[i];
         float *o = out + e * post * stride + f;
         for (int d = 0; d < ndeg; d++) {
-            const float rad = x * kPiF * exp2f((float)d);
             float s, c;
-            sincosf(rad, &s, &c);
+            posenc_sincos(x, d, s, c);
             o[(int64_t)(2 * d) * post] = s;
             o[(int64_t)(2 * d + 1) * post] = c;
         }

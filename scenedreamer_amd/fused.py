@@ -554,11 +554,60 @@ def prepare_sky(R):
     with torch.cuda.device(R.dev):
         capi.check(lib.sdn_sky_pack_weights(w1.data_ptr(), ptrs, wc.data_ptr(), packed.data_ptr(), _stream(R.dev)))
         capi.check(lib.sdn_sky_pack_weights_mx(w1.data_ptr(), ptrs, wc.data_ptr(), packed_mx.data_ptr(), _stream(R.dev)))
-    consts = torch.cat([w["sky_net.fc1.bias"] + R.sky_z.reshape(-1)] + [w[f"sky_net.fc{i}.bias"] for i in (2, 3, 4, 5)] +
-                       [w["sky_net.fc_out_c.bias"]]).contiguous()
-    assert consts.numel() == lib.sdn_sky_consts_floats()
+    consts = _sky_consts(R)
     R._fused_sky = dict(packed=packed, packed_mx=packed_mx, consts=consts, keep=(wh, w1, wc))
     return R._fused_sky
+
+
+def _sky_consts(R):
+    """The constant block of the sky kernels (sdn_sky_consts_floats): fc1.bias + fc_z_a(z) | fc2 .. fc5 bias | fc_out_c.bias."""
+    w = R.w
+    consts = torch.cat([w["sky_net.fc1.bias"] + R.sky_z.reshape(-1)] + [w[f"sky_net.fc{i}.bias"] for i in (2, 3, 4, 5)] +
+                       [w["sky_net.fc_out_c.bias"]]).contiguous()
+    assert consts.numel() == _lib().sdn_sky_consts_floats()
+    return consts
+
+
+def prepare_sky_exact(R):
+    """The sky MLP's weights as plain f32 in the order sky_f32_kernel consumes them + its constant block for the current style code
+    (dropped wherever prepare_sky's are).  No trunk shift, no f16 anywhere: no restriction on the weights' range, nothing to check."""
+    lib = _lib()
+    w = R.w
+    packed = torch.empty(lib.sdn_sky_f32_packed_weight_bytes(), dtype=torch.uint8, device=R.dev)
+    wh = [w[f"sky_net.fc{i}.weight"].to(torch.float32).contiguous() for i in (2, 3, 4, 5)]
+    ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in wh])
+    w1 = w["sky_net.fc1.weight"].to(torch.float32).contiguous()
+    wc = w["sky_net.fc_out_c.weight"].to(torch.float32).contiguous()
+    assert tuple(w1.shape) == (256, 33) and tuple(wc.shape) == (64, 256) and all(tuple(t.shape) == (256, 256) for t in wh)
+    with torch.cuda.device(R.dev):
+        capi.check(lib.sdn_sky_pack_weights_f32(w1.data_ptr(), ptrs, wc.data_ptr(), packed.data_ptr(), _stream(R.dev)),
+                   "sdn_sky_pack_weights_f32")
+    R._fused_sky_f32 = dict(packed=packed, consts=_sky_consts(R).to(torch.float32), keep=(wh, w1, wc))
+    return R._fused_sky_f32
+
+
+def sky_exact(R, rd, encoded=False, mean=True, n_workgroups=0):
+    """sky_fused's result from the fp32 kernel (csrc/sky_f32.hip): sky_c [n,64] and the frame mean sky_avg [1,64] for ray directions
+    rd [n,3], or (encoded) for SKYMLP.forward's own argument [n,33] -- the same bits either way, given ops.positional_encoding's
+    rows.  Every product is an f32 x f32 fmaf in a fixed order; the mean is a depth-5 f32 tree over each 32-ray tile, then f64, in
+    a fixed order.  The weights need not fit f16 (no TrunkRangeError) and nothing is calibrated.
+    mean=False: no frame mean (sky_avg is None), for a band that owns only part of the frame's rays."""
+    sk = getattr(R, "_fused_sky_f32", None) or prepare_sky_exact(R)
+    rd = rd.contiguous()
+    n = rd.shape[0]
+    if not (rd.dim() == 2 and rd.shape[1] == (33 if encoded else 3) and rd.dtype == torch.float32 and rd.is_cuda and rd.device == R.dev and n > 0):
+        raise ValueError(f"sky_exact: needs float32 [n,{33 if encoded else 3}] on {R.dev}, n > 0")
+    lib = _lib()
+    sky_c = torch.empty((n, 64), dtype=torch.float32, device=R.dev)
+    part = torch.empty((lib.sdn_sky_f32_partial_rows(n, n_workgroups), 64), dtype=torch.float64, device=R.dev)
+    sky_avg = torch.empty((1, 64), dtype=torch.float32, device=R.dev) if mean else None
+    if mean and "counter" not in sk:
+        sk["counter"] = torch.zeros(1, dtype=torch.int32, device=R.dev)     # the kernel leaves it at zero
+    with torch.cuda.device(R.dev):
+        capi.check(lib.sdn_sky_mlp_f32(rd.data_ptr(), sk["packed"].data_ptr(), sk["consts"].data_ptr(), sky_c.data_ptr(), part.data_ptr(),
+                                       n, n_workgroups, sky_avg.data_ptr() if mean else None, sk["counter"].data_ptr() if mean else None,
+                                       1 if encoded else 0, _stream(R.dev)), "sdn_sky_mlp_f32")
+    return sky_c, sky_avg
 
 
 def sky_terms(R):

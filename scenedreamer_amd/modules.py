@@ -50,7 +50,7 @@ class Backend:
         self.dev = None
         self.w = {}
         self.M, self.sample_depth, self.dists_scale, self.pad = 6, 3.0, 0.25, 0
-        self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = None
+        self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = self._fused_sky_f32 = None
         self.cnn_calibration = None
         self._bound = {}
         self._zkey = {}
@@ -77,7 +77,7 @@ class Backend:
         if self.dev is not None and self.dev != dev:
             self.w = {k: v for k, v in self.w.items() if k.startswith(prefix)}
             self._bound.clear()
-            self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = None
+            self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = self._fused_sky_f32 = None
             self.__dict__.pop("_mfma_cnns", None)
         self.dev = dev
         self._bound[prefix] = (module, key)
@@ -224,7 +224,10 @@ class LightningMLPNative:
 
 
 class SKYMLPNative:
-    """forward(x [N,...,33] positional-encoded ray directions, z [N,style]) -> c [N,...,64]."""
+    """forward(x [N,...,33] positional-encoded ray directions, z [N,style]) -> c [N,...,64].
+    Opt-in `module.sdn_exact = True` (or SDN_SKY_EXACT=1): the call runs on the fp32 MFMA kernel (sdn_sky_mlp_f32) -- weights of any
+    range natively (no TrunkRangeError), no sky gate, a fixed summation order; at 1/16 of the f16 matrix rate, and no accuracy gain
+    on weights the default kernel accepts."""
     _sdn_native = True
 
     def native_reason(self, x, z):
@@ -254,6 +257,7 @@ class SKYMLPNative:
             return torch.empty(shape, dtype=torch.float32, device=x.device)
         src = getattr(x, "_sdn_pe_src", None)    # set by ops.positional_encoding: (input, its version, ndegrees, dim, incl_orig, out version)
         results = []
+        exact = bool(self.__dict__.get("sdn_exact", os.environ.get("SDN_SKY_EXACT", "0") not in ("0", "", "false")))
         with torch.no_grad():
             for i in range(x.shape[0]):
                 B.style("sky_net.", z, i, fold_sky_net)
@@ -262,7 +266,10 @@ class SKYMLPNative:
                         src[3] in (-1, src[0].dim() - 1) and src[0]._version == src[1] and x._version == src[5] and
                         src[0].is_contiguous() and src[0].numel() == per * 3):
                     rd = src[0].detach().reshape(per, 3)
-                if rd is not None:
+                if exact:       # the fp32 kernel, either input form (the same bits): no gate, no range check
+                    sky_c, _ = (fused.sky_exact(B, rd, mean=False) if rd is not None else
+                                fused.sky_exact(B, x[i].reshape(per, 33), encoded=True, mean=False))
+                elif rd is not None:
                     # the argument IS positional_encoding(rd, 5, -1, True) (this package's op produced it and nobody wrote to it
                     # since): the kernel evaluates the encoding itself, and the per-ray result is kept for
                     # Generator._forward_perpix, which asks for sky_net of the very same rays again for every tile

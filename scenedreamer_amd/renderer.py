@@ -68,6 +68,7 @@ def fold_sky_net(R, z):
     with torch.no_grad():
         R.sky_z = F.linear(z, R.w["sky_net.fc_z_a.weight"])
     R._fused_sky = None
+    R._fused_sky_f32 = None
 
 
 def fold_denoiser(R, z):
@@ -103,6 +104,22 @@ class Renderer:
     def _resolve_cnn_mode(self, path, cnn_mode):
         """Which render CNN runs on `path` (the path actually taken: "fused", "exact" or "unfused")."""
         return resolve_cnn_mode(path, cnn_mode, self._exact_cnn_mode() if (cnn_mode is None and path == "exact") else "torch")
+
+    # The sky MLP of the "exact" path, the twin of exact_cnn: "torch" = sky_features + a library mean (default); "f32" =
+    # fused.sky_exact, the fp32 MFMA kernel (csrc/sky_f32.hip) with the frame mean finished inside it.  None = the environment
+    # variable SDN_EXACT_SKY, else "torch".  "fused" keeps sky_fused, "unfused" stays on PyTorch.  Every rank of a distributed job
+    # must be given the same value: the two differ by fp32 rounding.
+    exact_sky = None
+
+    def _exact_sky_mode(self):
+        v = self.exact_sky if self.exact_sky is not None else os.environ.get("SDN_EXACT_SKY", "torch")
+        if v not in EXACT_SKY_MODES:
+            raise ValueError(f"Renderer.exact_sky (or SDN_EXACT_SKY) must be 'torch' or 'f32', not {v!r}")
+        return v
+
+    def _resolve_sky_mode(self, path):
+        """Which sky MLP runs on `path` (the path actually taken: "fused", "exact" or "unfused")."""
+        return resolve_sky_mode(path, self._exact_sky_mode() if path == "exact" else "torch")
 
     def f32_cnn(self):
         """The fp32 MFMA render CNN (cnn.F32CNN), cached beside the f16 forms (the same events drop it)."""
@@ -656,7 +673,12 @@ class Renderer:
         if mode == "unfused":
             return "f32"
         if mode == "exact":
-            return "f32 (field: hash grid + f32-input MFMA with f32 accumulate; sky MLP and render CNN: PyTorch)"
+            sky, cnn = self._exact_sky_mode(), self._exact_cnn_mode()
+            if sky == "torch" and cnn == "torch":
+                return "f32 (field: hash grid + f32-input MFMA with f32 accumulate; sky MLP and render CNN: PyTorch)"
+            native = "f32-input MFMA with f32 accumulate"
+            return (f"f32 (field: hash grid + {native}; sky MLP: {native if sky == 'f32' else 'PyTorch'}; "
+                    f"render CNN: {native if cnn == 'f32' else 'PyTorch'})")
         from . import fused
         ct, _ = fused.precision_profile(self)
         cal = getattr(self, "cnn_calibration", None)
@@ -887,9 +909,13 @@ class Renderer:
         n = (p1 - p0) * Wp
         vid, d2, rd = vid.view(n, self.M), d2.view(2, n, self.M), rd.view(n, 3)
         with torch.no_grad():
-            if mode == "fused":
+            sky_mode = self._resolve_sky_mode(mode)
+            if sky_mode == "fused":
                 from . import fused
                 sky_c, _ = fused.sky_fused(self, rd)
+            elif sky_mode == "f32":      # (no frame mean from the kernel: the band owns only part of the frame's rays)
+                from . import fused
+                sky_c, _ = fused.sky_exact(self, rd, mean=False)
             else:
                 sky_c = self.sky_features(rd)
             sky_sum = sky_c[(own0 - p0) * Wp:(own1 - p0) * Wp].sum(dim=0, dtype=torch.float64)
@@ -970,9 +996,13 @@ class Renderer:
                     if mode == "unfused":                # fp32 MFMA kernel ("exact", Renderer.fallback)
                         cam_ori = cam_ori.to(self.dev)
             cnn_mode = self._resolve_cnn_mode(mode, cnn_mode)      # (validated before any work is done)
-            if mode == "fused":
+            sky_mode = self._resolve_sky_mode(mode)
+            if sky_mode == "fused":
                 from . import fused
                 sky_c, sky_avg = fused.sky_fused(self, rd)
+            elif sky_mode == "f32":
+                from . import fused
+                sky_c, sky_avg = fused.sky_exact(self, rd)
             else:
                 sky_c = self.sky_features(rd)
                 sky_avg = sky_c.mean(dim=0, keepdim=True)    # full-frame mean, scenedreamer.py:592-598
@@ -1173,6 +1203,7 @@ def _render_frames(self, poses, resolution_hw=(540, 960), num_samples=24, mode="
 Renderer.render_frames = _render_frames
 
 EXACT_CNN_MODES = ("torch", "f32")
+EXACT_SKY_MODES = ("torch", "f32")
 CNN_MODES = ("mfma", "torch", "f32")
 
 
@@ -1191,6 +1222,20 @@ def resolve_cnn_mode(path, cnn_mode=None, exact_cnn="torch"):
     if path == "fused":
         return "mfma"
     return exact_cnn if path == "exact" else "torch"
+
+
+def resolve_sky_mode(path, exact_sky="torch"):
+    """Which sky MLP runs: path = the path actually taken ("fused"; "exact" / "unfused", asked for or adopted by a closed gate through
+    Renderer.fallback), exact_sky = Renderer.exact_sky resolved.  Returns "fused" (fused.sky_fused, the f16-split kernel), "f32"
+    (fused.sky_exact, the fp32 MFMA kernel) or "torch" (Renderer.sky_features + mean)."""
+    if path not in ("fused", "exact", "unfused"):
+        raise ValueError(path)
+    if exact_sky not in EXACT_SKY_MODES:
+        raise ValueError(f"exact_sky must be 'torch' or 'f32', not {exact_sky!r}")
+    if path == "fused":
+        return "fused"
+    return exact_sky if path == "exact" else "torch"
+
 
 RECHECK_MIN_FRAMES = 2     # trajectories at least this long re-check the adopted CNN rung on their last frame (Renderer.recheck_cnn)
 FRONT_DEFAULT = "early"

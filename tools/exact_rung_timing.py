@@ -4,12 +4,16 @@ scene 2048, pose 0 of pattern 0, synthetic weights, style 8888), and writes prof
 
     python tools/exact_rung_timing.py [--reps 10] [--warmup 3] [--out profiles/exact_rung_timing.json] [--only cnn]
 
-Three comparisons, each inside ONE process on one device (devices differ by up to 20 %):
+Four comparisons, each inside ONE process on one device (devices differ by up to 20 %):
   field   fused.field_exact  vs  Renderer.field_unfused over the rays of the same (minimal-apron) window
   frame   render_frame(mode="exact")  vs  render_frame(mode="unfused")
   cnn     cnn.F32CNN (csrc/cnn_f32.hip)  vs  Renderer.render_cnn (PyTorch) on the same 548 x 968 net_out, and
           render_frame(mode="exact") with exact_cnn = "f32" vs "torch"; the kernel's per-launch times, and its time against the
           matrix-issue floor of the CNN: pixels x 5 015 040 FLOP / (1 024 SIMDs x 64 FLOP per clock x the clock)
+  sky     fused.sky_exact (csrc/sky_f32.hip)  vs  Renderer.sky_features + .mean() (PyTorch) on the rays of the same 548 x 968 frame
+          (the minimal-apron frame's ray count; sky_c and the frame mean on both sides), and the kernel's time against its
+          matrix-issue floor: 128-ray groups x 4 waves x chunks issued (fc1's padding included) x 128 MFMAs x 64 cycles / 1 024
+          SIMDs / the clock
 --only STEP runs one comparison and replaces only its key in an existing record.
 Every figure is the median of `reps` HIP-event timings after `warmup` runs, the two sides interleaved; `faster` is true when the
 gain exceeds the spread (max - min) of either side.  The field kernel's time is also set against its matrix-issue floor: evaluated
@@ -25,7 +29,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HW, NS, SCENE = (540, 960), 24, 2048
 MFMA_PER_TILE_PASS, MFMA_CYCLES, SIMDS, CLOCK_GHZ = 5888, 64, 1024, 2.4     # the clock: the part's maximum, so the fraction is a lower bound
-STEP_TIMEOUT_S = {"field": 420, "frame": 420, "cnn": 420}
+STEP_TIMEOUT_S = {"field": 420, "frame": 420, "cnn": 420, "sky": 300}
+SKY_CHUNKS, MFMA_PER_CHUNK = 2 + 4 * 8 + 2, 128      # csrc/sky_f32.hip: fc1 padded to K = 64 (2 chunks) | fc2 .. fc5 | fc_out_c
+SKY_FLOP_PER_RAY = 2 * (33 * 256 + 4 * 256 * 256 + 256 * 64)
 CNN_FLOP_PER_PIXEL, F32_FLOP_PER_CLOCK_PER_SIMD = 5015040, 64
 
 
@@ -150,16 +156,51 @@ def step_cnn(reps, warmup):
                 frame=dict(max_abs_diff_image=fdiff, render_frame_exact_cnn_f32=fn_, render_frame_exact_cnn_torch=fo_, **fcmp))
 
 
+def step_sky(reps, warmup):
+    torch, R, pose = _setup()
+    from scenedreamer_amd import fused
+    from scenedreamer_amd.renderer import CNN_HALO
+    with torch.no_grad():
+        _, _, rd, (Hp, Wp) = R.cast_rays(pose, HW)
+        o = R.pad // 2 - CNN_HALO
+        rows, cols = Hp - 2 * o, Wp - 2 * o                                 # 548 x 968
+        rd = rd.view(Hp, Wp, 3)[o:o + rows, o:o + cols].reshape(rows * cols, 3).contiguous()
+        n = rd.shape[0]
+
+        def exact():
+            return fused.sky_exact(R, rd)
+
+        def torch_seq():
+            c = R.sky_features(rd)
+            return c, c.mean(dim=0, keepdim=True)
+
+        (c0, a0), (c1, a1) = exact(), torch_seq()
+        diff_c, diff_avg = float((c0 - c1).abs().max()), float((a0 - a1).abs().max())
+        new, old = _time_pair(torch, exact, torch_seq, reps, warmup)
+    n_, o_, cmp_ = _summary(new, old)
+    groups = -(-n // 128)
+    rounds = -(-groups // min(groups, 256))          # a workgroup's trips through the group loop: the launch is as long as the longest
+    mfma_per_wave = SKY_CHUNKS * MFMA_PER_CHUNK
+    floor_ms = groups * 4 * mfma_per_wave * MFMA_CYCLES / SIMDS / (CLOCK_GHZ * 1e6)
+    return dict(frame=[rows, cols], rays=n, flop_per_ray=SKY_FLOP_PER_RAY, max_abs_diff_sky_c=diff_c, max_abs_diff_sky_avg=diff_avg,
+                sky_exact=n_, sky_features_torch=o_, **cmp_, ratio_kernel_over_torch=n_["median_ms"] / o_["median_ms"],
+                groups_of_128_rays=groups, chunks_per_group=SKY_CHUNKS, mfma_per_wave_and_group=mfma_per_wave,
+                fc1_padding_fraction_of_issue=(2 * MFMA_PER_CHUNK - 17 * 8) / mfma_per_wave, rounds_of_256_workgroups=rounds,
+                matrix_floor_ms=floor_ms, matrix_floor_ms_whole_rounds=rounds * mfma_per_wave * MFMA_CYCLES / (CLOCK_GHZ * 1e6),
+                clock_ghz_assumed=CLOCK_GHZ, matrix_issue_fraction=floor_ms / n_["median_ms"],
+                tflops=n * SKY_FLOP_PER_RAY / n_["median_ms"] / 1e9)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "exact_rung_timing.json"))
-    ap.add_argument("--step", choices=["field", "frame", "cnn"], help="(internal) run one comparison in this process and print its JSON")
-    ap.add_argument("--only", choices=["field", "frame", "cnn"], help="run this comparison only; the other keys of an existing --out file are kept")
+    ap.add_argument("--step", choices=["field", "frame", "cnn", "sky"], help="(internal) run one comparison in this process and print its JSON")
+    ap.add_argument("--only", choices=["field", "frame", "cnn", "sky"], help="run this comparison only; the other keys of an existing --out file are kept")
     args = ap.parse_args()
     if args.step:
-        res = {"field": step_field, "frame": step_frame, "cnn": step_cnn}[args.step](args.reps, args.warmup)
+        res = {"field": step_field, "frame": step_frame, "cnn": step_cnn, "sky": step_sky}[args.step](args.reps, args.warmup)
         print("RESULT " + json.dumps(res))
         return 0
     if args.reps < 10 or args.warmup < 3:
@@ -169,7 +210,7 @@ def main():
     if args.only and os.path.exists(args.out):
         with open(args.out) as f:
             rec = {**json.load(f), "config": rec["config"]}
-    for step in ((args.only,) if args.only else ("field", "frame", "cnn")):
+    for step in ((args.only,) if args.only else ("field", "frame", "cnn", "sky")):
         cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps),
                "--warmup", str(args.warmup)]
         r = subprocess.run(cmd, capture_output=True, text=True)
