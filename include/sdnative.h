@@ -320,6 +320,26 @@ int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const flo
                          int32_t n_rays, int32_t max_blocks, int32_t num_samples, float sample_depth, float dists_scale,
                          const void *packed, const float *consts, const float *sky_c, const float *sky_avg, float *net_out,
                          int32_t n_workgroups, const int32_t *window_host, const float *cam_ori_dev, sdn_stream_t stream);
+/* sdn_field_render_f32 with the two things it leaves out: the other return values of Generator._forward_perpix and the
+ * training-time stratified sampling.  The arguments of sdn_field_render_f32 up to cam_ori_dev, with the same meaning, then
+ *   strat_division: 0 or 1, as for sdn_field_encode (SDN_ERR_INVALID otherwise); read only with u_dev.
+ *   u_dev: NULL (deterministic), or dev f32 [n_rays, num_samples+1] = the caller's torch.rand draw, indexed by the launch's
+ *     row-major ray as in sdn_field_render; lin_dev is then linspace(0,1,num_samples+2)[:-1].  Not with a blocked == 2 window
+ *     (SDN_ERR_INVALID), the rule of sdn_field_render.
+ *   aux: NULL, or the sdn_field_aux of sdn_field_render: each of weights / depth / sigma / colour / sky_blended / nosky that is set
+ *     receives that return value for the rays of this launch, in the window's row-major order.  colour_passes != NULL or
+ *     flags != 0 is SDN_ERR_UNSUPPORTED: the fp32 kernel has no colour-branch skipping to count or to switch off.
+ * When any of the six is set the launch is the kernel's FIELD_AUX instantiation: no 32-ray group is skipped and rays that hit
+ * nothing are gathered too (the reference evaluates them).  When none is, it is the instantiation sdn_field_render_f32
+ * launches: with aux == NULL and u_dev == NULL this call IS sdn_field_render_f32.  net_out and every aux array are the same bits
+ * per ray whatever the window, the ray order or the schedule. */
+int sdn_field_render_f32_aux(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024,
+                             const float *table3, uint32_t table_rows, const float *scales_dev, const float *genc_host,
+                             const float *cam_ori_host, const float *voxel_dims_host, const float *lin_dev, const float *u_dev,
+                             int32_t n_rays, int32_t max_blocks, int32_t num_samples, float sample_depth, float dists_scale,
+                             const void *packed, const float *consts, const float *sky_c, const float *sky_avg, float *net_out,
+                             int32_t n_workgroups, const int32_t *window_host, const float *cam_ori_dev, int32_t strat_division,
+                             const sdn_field_aux *aux, sdn_stream_t stream);
 /* LightningMLP.forward as an op (layers.py:92-126), the arguments of sdn_render_mlp without colour_terms and ticket:
  * x dev f32 [n_rows,128], label dev u8 [n_rows] -> sigma dev f32 [n_rows] (fc_sigma, :115), c dev f32 [n_rows,64] (fc_out_c, :125) */
 int sdn_render_mlp_f32(const float *x, const uint8_t *label, const void *packed, const float *consts, float *sigma, float *c,

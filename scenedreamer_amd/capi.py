@@ -70,6 +70,9 @@ _SIGNATURES = {
     "sdn_field_pack_weights_f32": (c_i, [c_p, c_p, c_p, c_p, c_p]),
     "sdn_field_render_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_u, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int32, ctypes.c_int32,
                                    ctypes.c_int32, c_f, c_f, c_p, c_p, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, c_p]),
+    "sdn_field_render_f32_aux": (c_i, [c_p, c_p, c_p, c_p, c_p, c_u, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32, c_f, c_f, c_p, c_p, c_p, c_p, c_p, ctypes.c_int32, c_p, c_p, ctypes.c_int32,
+                                       c_p, c_p]),
     "sdn_render_mlp_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, ctypes.c_int32, c_p]),
     "sdn_sky_packed_weight_bytes": (ctypes.c_size_t, []),
     "sdn_sky_consts_floats": (ctypes.c_size_t, []),

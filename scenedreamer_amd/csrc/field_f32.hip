@@ -12,6 +12,10 @@
 //                             fc_2 .. fc_4 -> fc_sigma, fc_5, fc_6, fc_out_c, then the compositing epilogue mlp_kernel runs too
 //                             (field_composite.h: ONE definition of the volume rendering and the sky blend).  Every sample
 //                             of every ray that hits something is evaluated: no early termination, no colour-branch skipping.
+//   field_f32_kernel<FIELD_AUX>  the same, plus the other return values of Generator._forward_perpix (scenedreamer.py:429-430) per
+//                             sample -- weights, rand_depth, net_out_s, net_out_c -- and per ray -- the blended sky features, nosky_mask --
+//                             like field.hip's MODE_FUSED_AUX: no group is skipped and rays that hit nothing are gathered too (the
+//                             reference evaluates them).
 //   field_f32_kernel<RAW>     rows x [n,128] + label u8 [n] -> sigma [n], c [n,64].
 //   pack_f32_kernel           the folded weights in the order the kernel consumes them.
 //
@@ -45,7 +49,7 @@ constexpr int F32_LDS_LIN = F32_LDS_SCALES + NLEV * 4;
 constexpr int F32_LDS_LUT = F32_LDS_LIN + MAX_LIN * 4;
 constexpr int F32_LDS_TOTAL = F32_LDS_LUT + 1024;
 
-constexpr int F32_FIELD = 0, F32_RAW = 1;
+constexpr int F32_FIELD = 0, F32_RAW = 1, F32_FIELD_AUX = 2;
 
 struct F32Params {
     const float *wpk;          // packed f32 weights (pack_f32_kernel)
@@ -60,11 +64,18 @@ struct F32Params {
     const float *x;            // RAW: [R, 128]
     const uint8_t *label;      // RAW: [R]
     float *sigma_out;          // RAW: [R]
+    // FIELD_AUX: the other return values of Generator._forward_perpix, each optional (field.hip MlpParams has the same six)
+    float *w_out;              // [R][ns]     weights, * !sky_only (scenedreamer.py:373-376)
+    float *depth_out;          // [R][ns]     rand_depth after the NaN / inf -> 0 replacement (:350-352)
+    float *sig_out;            // [R][ns]     net_out_s (layers.py:115)
+    float *col_out;            // [R][ns][64] net_out_c (layers.py:125)
+    float *skyb_out;           // [R][64]     skynet_out_c after the keep_sky_out blend (:401)
+    uint8_t *nosky_out;        // [R]         nosky_mask (:382-383)
 };
 
 template <int MODE>
 __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
-    constexpr bool RAW = MODE == F32_RAW;
+    constexpr bool RAW = MODE == F32_RAW, AUX = MODE == F32_FIELD_AUX;
     // The two weight buffers are two OBJECTS on purpose: hipcc's wait insertion then knows that the LDS-DMA into one cannot
     // alias the fragment reads from the other and waits for the DMA (vmcnt) only at the __syncthreads() that ends the chunk.
     // As halves of one array every first fragment read of a chunk waited for the prefetch issued just before it.
@@ -95,7 +106,8 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
         uint8_t flag = 0;                                  // bit 0 sky_only, bit 1 nosky
         if constexpr (!RAW) flag = (ray_ok && enc.voxel_id[(size_t)rr * enc.M] != 0) ? (uint8_t)0 : (uint8_t)1;   // scenedreamer.py:337
         // a group none of whose 32 rays hits anything is skipped: every weight is exactly zero (:376)
-        const bool grp_hit = RAW ? true : __syncthreads_or(!(flag & 1)) != 0;
+        // (AUX also returns the per-sample sigma / colour of rays that hit nothing, so it skips no group)
+        const bool grp_hit = (RAW || AUX) ? true : __syncthreads_or(!(flag & 1)) != 0;
         bool gnd = false;
         float outq[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         float carry = 0.f, tsum = 0.f;
@@ -103,6 +115,7 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
         for (int ch = 0; grp_hit && ch < p.nch; ch++) {
             int lab;
             float dist = 0.f;
+            float smp_depth = 0.f;   // AUX: this lane's sample depth
             float feat[8][8];
             const long row = (long)(tile_ok ? tile : 0) * 256 + ch * 32 + j;   // RAW: this lane's row
             if constexpr (RAW) {
@@ -123,7 +136,8 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
                 gnd = gnd || es.gnd;
                 lab = es.label;
                 dist = es.dist;
-                const bool use_feat = !(flag & 1);
+                if constexpr (AUX) smp_depth = es.depth;
+                const bool use_feat = AUX ? ray_ok : !(flag & 1);
                 // Gathers in flight per lane: 2 levels (32 x 16 B), then one at a time (field_kernel: 4 levels).  The features stay
                 // f32 here -- 64 registers per lane by the end of the stage -- and a pass is 377 k matrix cycles long: a few more round
                 // trips to L2 cost little, spilling would cost more
@@ -211,6 +225,20 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
             // ---- volume rendering + this pass's share of the ray's colour (field_composite.h) ------------------------------------
             const float wgt = render_weight(sigma, dist, q, carry);
             tsum += wgt;
+            if constexpr (AUX) {   // the per-sample return values of Generator._forward_perpix
+                const int sidx = ch * SAMP_PER_STEP + q;
+                if (ray_ok && sidx < p.ns) {
+                    int ray_s = rl;   // (an opaque copy, as in the epilogue: the row is derived here, not carried through the pass)
+                    asm volatile("" : "+v"(ray_s));
+                    const size_t smp = (size_t)p.win.out_row(ray_s) * p.ns + sidx;
+                    if (h == 0) {
+                        if (p.w_out) p.w_out[smp] = (flag & 1) ? 0.f : wgt;
+                        if (p.depth_out) p.depth_out[smp] = smp_depth;
+                        if (p.sig_out) p.sig_out[smp] = sigma;
+                    }
+                    if (p.col_out) store_colour_row(p.col_out + smp * OUTC, col, h);
+                }
+            }
             accumulate_colour(col, wgt, q, outq);
         }
 
@@ -225,7 +253,8 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
             const int g = quad_any(gnd);
             const bool last_hit = ray_ok && enc.voxel_id[(size_t)rr_e * enc.M + (enc.M - 1)] != 0;
             if (last_hit || g) flag |= 2;
-            blend_sky_store<false>(cst, p.sky_c, p.net_out, rr_e, p.win.out_row(ray_e), ray_ok, tsum, flag, outq, q, h);
+            blend_sky_store<AUX>(cst, p.sky_c, p.net_out, rr_e, p.win.out_row(ray_e), ray_ok, tsum, flag, outq, q, h,
+                                 AUX ? p.skyb_out : nullptr, AUX ? p.nosky_out : nullptr);
         }
     }
     __syncthreads();   // (a pass's last fetch -- chunk 0 for a pass that never came -- lands before the LDS is released)
@@ -276,22 +305,28 @@ int sdn_field_pack_weights_f32(const float *w1, const float *const *wh5_host, co
     return sdn::check_launch("sdn_field_pack_weights_f32");
 }
 
-int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024, const float *table3,
-                         uint32_t table_rows, const float *scales_dev, const float *genc_host, const float *cam_ori_host,
-                         const float *voxel_dims_host, const float *lin_dev, const float *u_dev, int32_t n_rays, int32_t max_blocks,
-                         int32_t num_samples, float sample_depth, float dists_scale, const void *packed, const float *consts,
-                         const float *sky_c, const float *sky_avg, float *net_out, int32_t n_workgroups, const int32_t *window_host,
-                         const float *cam_ori_dev, sdn_stream_t stream) {
-    if (!(packed && consts && sky_c && net_out)) return sdn::fail(SDN_ERR_INVALID, "sdn_field_render_f32: null pointer");
-    if (u_dev) return sdn::fail(SDN_ERR_UNSUPPORTED, "sdn_field_render_f32: deterministic sampling only (u_dev must be NULL)");
+// the two field entries: argument checks, parameter fill, launch.  `stochastic`: the entry accepts u_dev
+static int render_f32(const char *who, bool stochastic, const int32_t *voxel_id, const float *depth2, const float *raydirs,
+                      const uint8_t *lut1024, const float *table3, uint32_t table_rows, const float *scales_dev, const float *genc_host,
+                      const float *cam_ori_host, const float *voxel_dims_host, const float *lin_dev, const float *u_dev, int32_t n_rays,
+                      int32_t max_blocks, int32_t num_samples, float sample_depth, float dists_scale, const void *packed,
+                      const float *consts, const float *sky_c, const float *sky_avg, float *net_out, int32_t n_workgroups,
+                      const int32_t *window_host, const float *cam_ori_dev, int32_t strat_division, const sdn_field_aux *aux,
+                      sdn_stream_t stream) {
+    if (!(packed && consts && sky_c && net_out)) return sdn::fail(SDN_ERR_INVALID, "%s: null pointer", who);
+    if (u_dev && !stochastic) return sdn::fail(SDN_ERR_UNSUPPORTED, "%s: deterministic sampling only (u_dev must be NULL)", who);
+    if (aux && (aux->colour_passes || aux->flags))
+        return sdn::fail(SDN_ERR_UNSUPPORTED, "%s: the fp32 kernel skips no colour branch (aux->colour_passes must be NULL, aux->flags 0)", who);
+    if (u_dev && window_host && window_host[5] == 2)
+        return sdn::fail(SDN_ERR_INVALID, "%s: stochastic sampling with the blocked == 2 ray order is not supported", who);
     static const float zero3[3] = {0.f, 0.f, 0.f};
     if (cam_ori_dev && !cam_ori_host) cam_ori_host = zero3;
     F32Params p{};
-    if (int rc = fill_enc(p.enc, "sdn_field_render_f32", voxel_id, depth2, raydirs, lut1024, table3, table_rows, scales_dev, genc_host,
-                          cam_ori_host, voxel_dims_host, lin_dev, nullptr, n_rays, max_blocks, num_samples, sample_depth, dists_scale, 0))
+    if (int rc = fill_enc(p.enc, who, voxel_id, depth2, raydirs, lut1024, table3, table_rows, scales_dev, genc_host, cam_ori_host,
+                          voxel_dims_host, lin_dev, u_dev, n_rays, max_blocks, num_samples, sample_depth, dists_scale, strat_division))
         return rc;
     int32_t launch_rays = n_rays;
-    if (int rc = set_window(p.win, window_host, n_rays, "sdn_field_render_f32", &launch_rays)) return rc;
+    if (int rc = set_window(p.win, window_host, n_rays, who, &launch_rays)) return rc;
     p.enc.win = p.win;
     p.R = p.enc.R = launch_rays;     // (a ragged blocked window walks its whole block grid: the extra positions are no rays)
     p.ns = num_samples;
@@ -299,8 +334,38 @@ int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const flo
     p.n_tiles = p.enc.n_tiles = sdn::div_up(launch_rays, RAYS_PER_TILE);
     p.wpk = (const float *)packed; p.consts = consts; p.sky_c = sky_c; p.sky_avg = sky_avg; p.net_out = net_out;
     p.cam_ori_dev = cam_ori_dev;
-    hipLaunchKernelGGL((field_f32_kernel<F32_FIELD>), dim3(field_workgroups(p.n_tiles, n_workgroups)), dim3(256), 0, (hipStream_t)stream, p);
-    return sdn::check_launch("sdn_field_render_f32");
+    const dim3 grid(field_workgroups(p.n_tiles, n_workgroups));
+    if (aux && (aux->weights || aux->depth || aux->sigma || aux->colour || aux->sky_blended || aux->nosky)) {
+        p.w_out = aux->weights; p.depth_out = aux->depth; p.sig_out = aux->sigma; p.col_out = aux->colour;
+        p.skyb_out = aux->sky_blended; p.nosky_out = aux->nosky;
+        hipLaunchKernelGGL((field_f32_kernel<F32_FIELD_AUX>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    } else {
+        hipLaunchKernelGGL((field_f32_kernel<F32_FIELD>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    }
+    return sdn::check_launch(who);
+}
+
+int sdn_field_render_f32(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024, const float *table3,
+                         uint32_t table_rows, const float *scales_dev, const float *genc_host, const float *cam_ori_host,
+                         const float *voxel_dims_host, const float *lin_dev, const float *u_dev, int32_t n_rays, int32_t max_blocks,
+                         int32_t num_samples, float sample_depth, float dists_scale, const void *packed, const float *consts,
+                         const float *sky_c, const float *sky_avg, float *net_out, int32_t n_workgroups, const int32_t *window_host,
+                         const float *cam_ori_dev, sdn_stream_t stream) {
+    return render_f32("sdn_field_render_f32", false, voxel_id, depth2, raydirs, lut1024, table3, table_rows, scales_dev, genc_host,
+                      cam_ori_host, voxel_dims_host, lin_dev, u_dev, n_rays, max_blocks, num_samples, sample_depth, dists_scale, packed,
+                      consts, sky_c, sky_avg, net_out, n_workgroups, window_host, cam_ori_dev, 0, nullptr, stream);
+}
+
+int sdn_field_render_f32_aux(const int32_t *voxel_id, const float *depth2, const float *raydirs, const uint8_t *lut1024,
+                             const float *table3, uint32_t table_rows, const float *scales_dev, const float *genc_host,
+                             const float *cam_ori_host, const float *voxel_dims_host, const float *lin_dev, const float *u_dev,
+                             int32_t n_rays, int32_t max_blocks, int32_t num_samples, float sample_depth, float dists_scale,
+                             const void *packed, const float *consts, const float *sky_c, const float *sky_avg, float *net_out,
+                             int32_t n_workgroups, const int32_t *window_host, const float *cam_ori_dev, int32_t strat_division,
+                             const sdn_field_aux *aux, sdn_stream_t stream) {
+    return render_f32("sdn_field_render_f32_aux", true, voxel_id, depth2, raydirs, lut1024, table3, table_rows, scales_dev, genc_host,
+                      cam_ori_host, voxel_dims_host, lin_dev, u_dev, n_rays, max_blocks, num_samples, sample_depth, dists_scale, packed,
+                      consts, sky_c, sky_avg, net_out, n_workgroups, window_host, cam_ori_dev, strat_division, aux, stream);
 }
 
 int sdn_render_mlp_f32(const float *x, const uint8_t *label, const void *packed, const float *consts, float *sigma, float *c,

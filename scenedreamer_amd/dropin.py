@@ -30,10 +30,20 @@ loop and Generator.forward only read `net_out`) the other eleven are None; with 
 produced (the field kernel's MODE_FUSED_AUX instantiation writes weights, rand_depth, net_out_s, net_out_c, the blended
 skynet_out_c and nosky_mask; new_dists / new_idx come from sdn_sample_depth, the sky masks from voxel_id) -- what
 inference_givenstyle_depth reads (scenedreamer.py:812-817); tile by tile then, without the one-evaluation-per-frame shortcut.
+
+The exact route.  A style whose trunk weights the packed f16 stream cannot hold (GeneratorBinding.style_refusal) goes to the
+reference's op-by-op method by default.  `binding(G, exact="refused")` (or SDN_PERPIX_EXACT=refused) serves such a style with
+the fp32 field kernel instead (fused.field_exact: sdn_field_render_f32 / sdn_field_render_f32_aux, no restriction on the
+weights' range); `exact=True` (SDN_PERPIX_EXACT=1) serves EVERY call that way and never packs the f16 stream.  The route covers
+what the fast one covers -- the 12-tuple with `aux`, the torch.rand draw of the training-time sampling, in-place tile windows,
+one evaluation per frame -- and is counted under stats["perpix_exact"].  Sky features it has to evaluate itself (a tile without
+the pre-pass) come from fused.sky_exact; those of the pre-pass are used as they come.  Calls why_not_perpix rejects still go
+to the reference method.
 """
 import importlib
 import importlib.abc
 import importlib.util
+import os
 import sys
 import types
 
@@ -47,11 +57,30 @@ PERPIX_OUTPUTS = ("net_out", "new_dists", "weights", "total_weights_raw", "rand_
                   "nosky_mask", "sky_mask", "sky_only_mask", "new_idx")
 
 
+def parse_exact(v):
+    """GeneratorBinding.exact from an argument or from SDN_PERPIX_EXACT's text: False (a refused style goes to the reference's
+    method), "refused" (a refused style is served by the fp32 field kernel), True (every call is).  None = the environment."""
+    if v is None:
+        v = os.environ.get("SDN_PERPIX_EXACT", "")
+    if isinstance(v, str):
+        t = v.strip().lower()
+        if t in ("", "0"):
+            return False
+        if t == "refused":
+            return "refused"
+        if t == "1":
+            return True
+    elif v is True or v is False:
+        return v
+    raise ValueError(f"exact (or SDN_PERPIX_EXACT) must be False / 0, 'refused' or True / 1, not {v!r}")
+
+
 class GeneratorBinding:
-    def __init__(self, aux=False):
+    def __init__(self, aux=False, exact=None):
         self.B = modules.Backend()
         self.aux = bool(aux)
-        self.stats = {"perpix_fast": 0, "perpix_reference": 0, "global_fast": 0, "global_reference": 0, "tiles_in_place": 0,
+        self.exact = parse_exact(exact)
+        self.stats = {"perpix_fast": 0, "perpix_exact": 0, "perpix_reference": 0, "global_fast": 0, "global_reference": 0, "tiles_in_place": 0,
                       "tiles_copied": 0, "sky_reused": 0, "sky_evaluated": 0, "frames_coalesced": 0, "tiles_from_frame": 0,
                       "cnn_tiles_from_frame": 0, "why": {}}
         self._scene_key = None
@@ -189,9 +218,10 @@ class GeneratorBinding:
         bases = (voxel_id.data_ptr() - ov * 4, depth2.data_ptr() - od * 4, raydirs.data_ptr() - orr * 4)
         return fused.Window(n_src, pitch, first, h, w), bases
 
-    def rays(self, G, voxel_id, depth2, raydirs):
+    def rays(self, G, voxel_id, depth2, raydirs, exact=False):
         """(window, voxel_id, depth2, raydirs, sky_c) for sdn_field_render: frame-wide arrays read in place through a window when
-        the sky features of the whole frame are at hand (SKYMLPNative keeps those of the pre-pass), else tile-local copies."""
+        the sky features of the whole frame are at hand (SKYMLPNative keeps those of the pre-pass), else tile-local copies.
+        exact: tile-local sky features come from the fp32 sky kernel (a refused sky style cannot raise there)."""
         B = self.B
         _, h, w, M, _ = voxel_id.shape
         last = G.sky_net.__dict__.get("_sdn_last_frame") if modules.is_native(G.sky_net) else None
@@ -216,13 +246,13 @@ class GeneratorBinding:
         vid = voxel_id.reshape(n, M).contiguous()
         d2 = depth2.reshape(2, n, M).contiguous()
         rd = raydirs.reshape(n, 3).contiguous()
-        sky_c, sky_mean = fused.sky_fused(B, rd)
+        sky_c, sky_mean = (fused.sky_exact if exact else fused.sky_fused)(B, rd)
         self.stats["tiles_copied"] += 1
         self.stats["sky_evaluated"] += 1
         return fused.Window(n), vid, d2, rd, sky_c, sky_mean
 
     # ------------------------------------------------------------------ one field / CNN evaluation per FRAME
-    def frame_field(self, G, last, win, bases, views, cam_ori_t, sky_avg, ns):
+    def frame_field(self, G, last, win, bases, views, cam_ori_t, sky_avg, ns, exact=False):
         """net_out [1,H0,W0,64] of the WHOLE frame the tile belongs to, evaluated once and kept for the frame's other tiles.
 
         inference_givenstyle cuts the padded frame into overlapping tiles (128 px + a 30-px apron, scenedreamer.py:600-616) and
@@ -234,12 +264,13 @@ class GeneratorBinding:
         the caching allocator reuses from frame to frame."""
         fr = self._frame
         key = (bases, tuple(v._version for v in views), cam_ori_t._version, ns, self.B._zkey.get("render_net."), self._scene_key,
-               self.B._bound["render_net."][1], float(self.B.sample_depth), float(self.B.dists_scale), int(self.B.M))
+               self.B._bound["render_net."][1], float(self.B.sample_depth), float(self.B.dists_scale), int(self.B.M), bool(exact))
         if (fr is not None and fr["last"] is last and fr["cam"] is cam_ori_t and fr["sky_avg"] is sky_avg and fr["key"] == key):
             return fr["net_out"]
         H0, W0 = win.n_src // win.pitch, win.pitch
-        net_out = fused.field_render(self.B, bases[0], bases[1], bases[2], cam_ori_t, last["sky_c"], sky_avg, ns,
-                                     window=fused.Window.crop(H0, W0, 0))     # the whole frame as a window: 8 x 4-pixel ray blocks (ragged: 990 columns)
+        field = fused.field_exact if exact else fused.field_render
+        net_out = field(self.B, bases[0], bases[1], bases[2], cam_ori_t, last["sky_c"], sky_avg, ns,
+                        window=fused.Window.crop(H0, W0, 0))     # the whole frame as a window: 8 x 4-pixel ray blocks (ragged: 990 columns)
         self._frame = dict(last=last, cam=cam_ori_t, sky_avg=sky_avg, key=key, net_out=net_out.view(1, H0, W0, 64), img=None, raw=None,
                            keep=views)
         self.stats["frames_coalesced"] += 1
@@ -299,10 +330,12 @@ def _render_net_reason(net):
     return None
 
 
-def binding(G, aux=None, term_eps=None):
+def binding(G, aux=None, term_eps=None, exact=None):
     """The generator's GeneratorBinding (created on first use).  aux: also produce the other eleven return values of
     _forward_perpix.  term_eps: early ray termination threshold of the field kernel for this generator (0 = evaluate every
-    sample exactly like the reference; default fused.TERM_EPS_DEFAULT, which moves net_out by at most 2 x eps = 1e-4)."""
+    sample exactly like the reference; default fused.TERM_EPS_DEFAULT, which moves net_out by at most 2 x eps = 1e-4).
+    exact: False / "refused" / True -- which calls the fp32 field kernel serves (parse_exact; a new binding starts from
+    SDN_PERPIX_EXACT, else False)."""
     b = G.__dict__.get("_sdn_binding")
     if b is None:
         b = G.__dict__["_sdn_binding"] = GeneratorBinding()
@@ -311,6 +344,8 @@ def binding(G, aux=None, term_eps=None):
     if term_eps is not None:
         b.B.term_eps = float(term_eps)
         b._frame = None
+    if exact is not None:
+        b.exact = parse_exact(exact)
     return b
 
 
@@ -324,8 +359,8 @@ def _count(b, key, why=None):
 # the two methods
 # ---------------------------------------------------------------------------------------------------------------------
 def fast_forward_perpix(self, blk_feats, voxel_id, depth2, raydirs, cam_ori_t, z, global_enc):
-    """Generator._forward_perpix (scenedreamer.py:313-430) on sdn_field_render.  Same arguments; returns the same 12-tuple
-    (see the module docstring for which entries are filled)."""
+    """Generator._forward_perpix (scenedreamer.py:313-430) on sdn_field_render -- or, on the exact route (GeneratorBinding.exact), on
+    the fp32 field kernel.  Same arguments; returns the same 12-tuple (see the module docstring for which entries are filled)."""
     b = binding(self)
     why = b.why_not_perpix(self, voxel_id, depth2, raydirs, cam_ori_t, z, global_enc)
     if why is not None:
@@ -333,10 +368,16 @@ def fast_forward_perpix(self, blk_feats, voxel_id, depth2, raydirs, cam_ori_t, z
         return self._forward_perpix_reference(blk_feats, voxel_id, depth2, raydirs, cam_ori_t, z, global_enc)
     _count(b, "perpix_fast")
     B = b.B
+    exact = b.exact is True
     with torch.no_grad():
         b.sync(self, z, global_enc)
-        why = b.style_refusal()
-        if why is not None:
+        why = None if exact else b.style_refusal()
+        if why is not None and b.exact == "refused":
+            exact, why = True, None
+        if exact:
+            b.stats["perpix_fast"] -= 1
+            _count(b, "perpix_exact")
+        elif why is not None:
             b.stats["perpix_fast"] -= 1
             _count(b, "perpix_reference", why)
     if why is not None:
@@ -344,7 +385,7 @@ def fast_forward_perpix(self, blk_feats, voxel_id, depth2, raydirs, cam_ori_t, z
     with torch.no_grad():
         _, h, w, M, _ = voxel_id.shape
         ns = int(self.num_samples)
-        win, vid, d2, rd, sky_c, sky_mean = b.rays(self, voxel_id, depth2, raydirs)
+        win, vid, d2, rd, sky_c, sky_mean = b.rays(self, voxel_id, depth2, raydirs, exact=exact)
         if hasattr(self, "sky_avg"):                          # the frame-wide pre-pass of inference_givenstyle, :592-598
             sky_avg = self.sky_avg
         else:                                                 # sky_global_avgpool over the rays of this call, :392-393
@@ -357,12 +398,13 @@ def fast_forward_perpix(self, blk_feats, voxel_id, depth2, raydirs, cam_ori_t, z
         if (b.coalesce and isinstance(sky_mean, dict) and u is None and aux is None and hasattr(self, "sky_avg") and
                 win.rows * win.cols < win.n_src and getattr(win, "pitch_known", True)):
             # a tile of a frame whose arrays (and sky features) are all at hand: the frame is evaluated once, tiles are views
-            full = b.frame_field(self, sky_mean, win, (vid, d2, rd), (voxel_id, depth2, raydirs), cam_ori_t, sky_avg, ns)
+            full = b.frame_field(self, sky_mean, win, (vid, d2, rd), (voxel_id, depth2, raydirs), cam_ori_t, sky_avg, ns, exact=exact)
             hb, wb = divmod(win.first, win.pitch)
             out[0] = full[:, hb:hb + h, wb:wb + w, :]
             b.stats["tiles_from_frame"] += 1
             return tuple(out)
-        net_out = fused.field_render(B, vid, d2, rd, cam_ori_t, sky_c, sky_avg, ns, u=u, window=win, aux=aux)
+        field = fused.field_exact if exact else fused.field_render
+        net_out = field(B, vid, d2, rd, cam_ori_t, sky_c, sky_avg, ns, u=u, window=win, aux=aux)
         out[0] = net_out.view(1, h, w, 64)
         if aux is not None:
             # the same values the reference returns (scenedreamer.py:335-352, :373-377); samples come from the stand-alone op
@@ -416,9 +458,10 @@ def fast_forward_global(self, net_out, z):
 # ---------------------------------------------------------------------------------------------------------------------
 # installation
 # ---------------------------------------------------------------------------------------------------------------------
-def accelerate(G, aux=False, term_eps=None):
+def accelerate(G, aux=False, term_eps=None, exact=None):
     """Bind the fast path to an existing reference generator: the classes of its render_net / sky_net / denoiser get the
-    native forwards (parameters untouched), its _forward_perpix / _forward_global become the methods above."""
+    native forwards (parameters untouched), its _forward_perpix / _forward_global become the methods above.
+    exact: see binding()."""
     for name in ("render_net", "sky_net", "denoiser"):
         modules.make_fast(type(getattr(G, name)))
     cls = type(G)
@@ -427,7 +470,7 @@ def accelerate(G, aux=False, term_eps=None):
         G._forward_global_reference = types.MethodType(cls._forward_global, G)
         G._forward_perpix = types.MethodType(fast_forward_perpix, G)
         G._forward_global = types.MethodType(fast_forward_global, G)
-    binding(G, aux=aux, term_eps=term_eps)
+    binding(G, aux=aux, term_eps=term_eps, exact=exact)
     return G
 
 

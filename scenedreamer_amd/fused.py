@@ -219,33 +219,67 @@ def _sky_avg(R, sky_avg):
     return sky_avg
 
 
-def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None):
+AUX_SHAPES = {"weights": (("n", "ns"), torch.float32), "depth": (("n", "ns"), torch.float32), "sigma": (("n", "ns"), torch.float32),
+              "colour": (("n", "ns", 64), torch.float32), "sky_blended": (("n", 64), torch.float32), "nosky": (("n",), torch.uint8)}
+
+
+def _aux_tensors(R, aux, n_rays, ns):
+    """The tensors a launch writes for the aux dict protocol of field_render / field_exact (keys from AUX_OUTPUTS; an empty dict =
+    "weights" + "depth"): allocated here, stored into `aux`, returned as the C struct."""
+    want = list(aux) or ["weights", "depth"]
+    assert all(k in AUX_SHAPES for k in want), want
+    dims = {"n": n_rays, "ns": ns}
+    for k in want:
+        shape, dtype = AUX_SHAPES[k]
+        aux[k] = torch.empty(tuple(dims.get(d, d) for d in shape), dtype=dtype, device=R.dev)   # (with aux the kernel visits every ray and sample)
+    return capi.FieldAux(**{k: aux[k].data_ptr() for k in want})
+
+
+def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None, u=None, division="reciprocal", aux=None):
     """field_render's result from the fp32 kernel (csrc/field_f32.hip): sample placement + hash-grid lookup by the same device
-    functions, the MLP as f32 x f32 fmaf chains on the f32-input MFMA, every sample evaluated.  Deterministic sampling only.
+    functions, the MLP as f32 x f32 fmaf chains on the f32-input MFMA, every sample evaluated.
     The weights need not fit f16 (no TrunkRangeError) and nothing here is calibrated; on weights the f16 kernels accept it is
     NOT closer to the reference than they are -- it is the native fallback for the styles they do not serve.
-    Arguments as for field_render (tensors only); net_out [window.n_rays, 64] in the window's row-major order."""
+    Arguments as for field_render: vid / d2 / rd / sky_c are tensors, or -- with a `window` -- plain device addresses (int) of
+    frame-wide arrays of window.n_src rays; u / division: the training-time stratified sampling (the launch then takes the
+    row-major ray order); aux: field_render's dict protocol for the other return values of Generator._forward_perpix (the
+    kernel's FIELD_AUX instantiation).  net_out [window.n_rays, 64] in the window's row-major order, like every aux array.
+    With u None and aux None the call is sdn_field_render_f32, as it was before either existed."""
     sc = R._fused_scene or prepare_scene(R)
     st = getattr(R, "_fused_style_f32", None) or prepare_style_f32(R)
     if window is None:
         window = Window(vid.shape[0])
     n_rays = window.n_rays
-    vid, d2, rd, sky_c = vid.contiguous(), d2.contiguous(), rd.contiguous(), sky_c.contiguous()
-    for t, rows, what in ((vid, 0, "voxel_id"), (d2, 1, "depth2"), (rd, 0, "raydirs"), (sky_c, 0, "sky_c")):
+
+    def addr(t, rows, what):
+        if isinstance(t, int):
+            return t
         if not (t.is_cuda and t.device == R.dev and t.shape[rows] == window.n_src):
             raise ValueError(f"{what} must hold the window's {window.n_src} source rays on {R.dev}")
+        return t.data_ptr()
+
+    vid, d2, rd, sky_c = (t if isinstance(t, int) else t.contiguous() for t in (vid, d2, rd, sky_c))
+    p_vid, p_d2, p_rd, p_sky = addr(vid, 0, "voxel_id"), addr(d2, 1, "depth2"), addr(rd, 0, "raydirs"), addr(sky_c, 0, "sky_c")
     sky_avg = _sky_avg(R, sky_avg)
     net_out = torch.empty((n_rays, 64), dtype=torch.float32, device=R.dev)
-    lin = _lin(R, ns)
+    if u is not None and not (u.is_cuda and u.device == R.dev and u.dtype == torch.float32 and tuple(u.shape) == (n_rays, ns + 1) and
+                              u.is_contiguous()):
+        raise ValueError(f"u must be a contiguous float32 [{n_rays}, {ns + 1}] on {R.dev}")
+    lin = _lin(R, ns, stratified=u is not None)
     ori, ori_dev = _cam_ori(R, cam_ori)
+    head = (p_vid, p_d2, p_rd, sc["lut"].data_ptr(), sc["table3"].data_ptr(), sc["T"], sc["scales"].data_ptr(), sc["genc"].ctypes.data,
+            ori.ctypes.data, sc["dims"].ctypes.data, lin.data_ptr(), u.data_ptr() if u is not None else None, n_rays, R.M, ns,
+            R.sample_depth, R.dists_scale, st["packed"].data_ptr(), st["consts"].data_ptr(), p_sky, sky_avg.data_ptr(),
+            net_out.data_ptr(), 0, window.host(0, n_rays, u is None), ori_dev.data_ptr() if ori_dev is not None else None)
     with torch.cuda.device(R.dev):
-        rc = _lib().sdn_field_render_f32(vid.data_ptr(), d2.data_ptr(), rd.data_ptr(), sc["lut"].data_ptr(), sc["table3"].data_ptr(),
-                                         sc["T"], sc["scales"].data_ptr(), sc["genc"].ctypes.data, ori.ctypes.data,
-                                         sc["dims"].ctypes.data, lin.data_ptr(), None, n_rays, R.M, ns, R.sample_depth,
-                                         R.dists_scale, st["packed"].data_ptr(), st["consts"].data_ptr(), sky_c.data_ptr(),
-                                         sky_avg.data_ptr(), net_out.data_ptr(), 0, window.host(0, n_rays, True),
-                                         ori_dev.data_ptr() if ori_dev is not None else None, _stream(R.dev))
-    capi.check(rc, "sdn_field_render_f32")
+        if u is None and aux is None:
+            rc, who = _lib().sdn_field_render_f32(*head, _stream(R.dev)), "sdn_field_render_f32"
+        else:
+            aux_c = _aux_tensors(R, aux, n_rays, ns) if aux is not None else None
+            rc = _lib().sdn_field_render_f32_aux(*head, {"reciprocal": 0, "ieee": 1}[division],
+                                                 ctypes.byref(aux_c) if aux_c is not None else None, _stream(R.dev))
+            who = "sdn_field_render_f32_aux"
+    capi.check(rc, who)
     return net_out
 
 
@@ -445,13 +479,7 @@ def field_render(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, passes=None, u=Non
     ori, ori_dev = _cam_ori(R, cam_ori)
     aux_c = None
     if aux is not None:
-        shapes = {"weights": ((n_rays, ns), torch.float32), "depth": ((n_rays, ns), torch.float32), "sigma": ((n_rays, ns), torch.float32),
-                  "colour": ((n_rays, ns, 64), torch.float32), "sky_blended": ((n_rays, 64), torch.float32), "nosky": ((n_rays,), torch.uint8)}
-        want = list(aux) or ["weights", "depth"]
-        assert all(k in shapes for k in want), want
-        for k in want:
-            aux[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=R.dev)     # (with aux the kernel visits every ray and sample)
-        aux_c = capi.FieldAux(**{k: aux[k].data_ptr() for k in want})
+        aux_c = _aux_tensors(R, aux, n_rays, ns)
     # ray order: 8 x 4 pixel blocks whenever the launch is a whole window -- also a ragged one (990 columns: the reference's padded
     # frame), unless the caller's per-group arrays are sized for the row-major groups or the sampling is stochastic
     ragged = u is None and all(t is None or t.numel() >= window.n_groups(ragged=True) for t in (passes, colour_passes))
