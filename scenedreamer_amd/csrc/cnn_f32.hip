@@ -7,29 +7,24 @@
 //   conv_f32_kernel<TAPS, CIN>   (9, 256) the 3x3 layers; (1, 256) conv4a / conv4b; (1, 64) conv1.
 //   pack_conv_f32_kernel         the OIHW weights in the order the kernel consumes them.
 //
-// Layout (field_f32.hip's): the layer is evaluated transposed, W as the A operand, the 32 pixels of a wave as columns, the 256
-// output channels as 8 accumulator blocks.  Lane l = (h = l >> 5, j = l & 31) holds A[i = j][k = h] and B[k = h][col j];
-// accumulator register r of block ib holds channel 32 ib + 8 (r / 4) + 4 h + r % 4 of pixel j.  A workgroup is 4 waves = 128
+// Lanes, the 8-block chunk, a convolution's stream and the chunk pipeline are mlp_f32.h's (the one statement of the layout): W as
+// the A operand, the 32 pixels of a wave as columns, the 256 output channels as 8 accumulator blocks.  A workgroup is 4 waves = 128
 // consecutive pixels of the row-major frame; pixel p is column p & 31 of wave (p >> 5) & 3 of group p >> 7.
 // Activations are plain f32 rows [H*W][C], no border: the B operand of a tap is read straight from the rows (64 B per lane and
 // chunk: channels 32 b + 16 h .. + 15 of the tap's pixel, one chunk ahead of the MFMAs that use it), and a tap that falls
 // outside the frame contributes 0.f -- F.conv2d(..., padding = 1).  The read always goes to an address inside the frame (clamped);
 // the zero is selected when the value is used, so that no MFMA waits for more than the barrier that ends the chunk before.
-// Weights: chunks of 32 KiB = one tap x 32 input channels x 256 outputs, TAPS * CIN / 32 per layer, L2 -> LDS (global_load_lds)
-// into the buffer the previous chunk left, shared by the 4 waves; one __syncthreads() per chunk (128 MFMAs per wave).
+// Weights: one chunk = one tap x 32 input channels x 256 outputs, TAPS * CIN / 32 per layer, multiplied by chunk_mul8_ahead.
 //
 // Summation order.  The MFMA is bit for bit a k-ordered fmaf chain.  One chain over the 2304 products of a 3x3 layer misses fp64
 // by 6.4 - 6.8 x the error of F.conv2d in fp32 (tests/cnn_f32_ref.py); so a tap's 256 products accumulate from ZERO in a second
 // accumulator set, which is then added to the running total on the VALU: taps in the order ky, kx; inside a tap the blocks b =
 // 0 .. 7; inside a block k-step kk = 0 .. 15 = channels 32 b + kk, then 32 b + 16 + kk.  A 1x1 layer is one chain.
-#include "mfma_common.h"
-#include "sdn_common.h"
+#include "mlp_f32.h"
 
 namespace {
 
 constexpr int COUT = 256;
-constexpr int CHUNK_BYTES = 32768;
-constexpr int CHUNK_FLOATS = CHUNK_BYTES / 4;
 constexpr int GROUP_PIXELS = 128;
 
 struct ConvF32Params {
@@ -46,56 +41,6 @@ struct ConvF32Params {
     float *out_raw;         // [3][H*W], or NULL
     int32_t H, W, n_groups;
 };
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; r++) z[r] = 0.f;
-    return z;
-}
-
-__device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-template <int K>
-__device__ __forceinline__ void chunk_piece(const char *lane_src, char *dst) {
-    // the immediate offset (below 4096) is added to the global AND to the LDS address
-    __builtin_amdgcn_global_load_lds((glb_char *)(lane_src + (K / 4) * 4096), (lds_char *)(dst + (K / 4) * 4096), 16, (K % 4) * 1024, 0);
-}
-
-// this wave's quarter of chunk `cp` -> weight buffer `wbuf`: 8 pieces of 1 KiB (64 lanes x 16 B), field_f32.hip's chunk_fetch
-__device__ __forceinline__ void chunk_fetch(const float *wpk, char *wbuf, int cp, int wave, unsigned lane16) {
-    const char *src = reinterpret_cast<const char *>(wpk) + (size_t)cp * CHUNK_BYTES + wave * 8192;    // uniform
-    char *dst = wbuf + wave * 8192;
-    asm volatile("" : "+v"(lane16));
-    chunk_piece<0>(src + lane16, dst); chunk_piece<1>(src + lane16, dst); chunk_piece<2>(src + lane16, dst); chunk_piece<3>(src + lane16, dst);
-    chunk_piece<4>(src + lane16, dst); chunk_piece<5>(src + lane16, dst); chunk_piece<6>(src + lane16, dst); chunk_piece<7>(src + lane16, dst);
-}
-
-// acc[ib] += sum over 16 k-steps of W_chunk[ib][k-step] x b[k-step].  A k-step's 2 KiB: [output blocks 0-3 | 4-7][lane][4 blocks].
-// The fragments of k-step kk + 1 are read while k-step kk is multiplied (pinned by the scheduling groups: left alone, hipcc
-// reads each float4 right in front of its four MFMAs and exposes an LDS round trip per four).
-__device__ __forceinline__ void chunk_mul8(const char *wbuf, int lane, const float (&b)[16], f32x16 (&acc)[8]) {
-    const float4 *w = reinterpret_cast<const float4 *>(wbuf) + lane;
-    float4 a0 = w[0], a1 = w[64];
-#pragma unroll
-    for (int kk = 0; kk < 16; kk++) {
-        float4 n0 = a0, n1 = a1;
-        if (kk < 15) { n0 = w[(kk + 1) * 128]; n1 = w[(kk + 1) * 128 + 64]; }
-        acc[0] = mfma_f32(a0.x, b[kk], acc[0]);
-        acc[1] = mfma_f32(a0.y, b[kk], acc[1]);
-        acc[2] = mfma_f32(a0.z, b[kk], acc[2]);
-        acc[3] = mfma_f32(a0.w, b[kk], acc[3]);
-        acc[4] = mfma_f32(a1.x, b[kk], acc[4]);
-        acc[5] = mfma_f32(a1.y, b[kk], acc[5]);
-        acc[6] = mfma_f32(a1.z, b[kk], acc[6]);
-        acc[7] = mfma_f32(a1.w, b[kk], acc[7]);
-        if (kk < 15) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // 2 LDS reads (k-step kk + 1)
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);                // 8 MFMAs (k-step kk)
-        a0 = n0; a1 = n1;
-    }
-}
 
 // The B operand of chunk (tap, blk) for this lane's pixel (y, x): 16 channels of the tap's pixel, from an address inside the frame.
 // Returns whether the tap's pixel IS inside the frame (the caller selects 0.f otherwise, when it uses the values).
@@ -130,8 +75,6 @@ __device__ __forceinline__ void arrived(float4 (&bv)[4]) {
     asm volatile("" : "+v"(bv[0].x), "+v"(bv[0].y), "+v"(bv[0].z), "+v"(bv[0].w), "+v"(bv[1].x), "+v"(bv[1].y), "+v"(bv[1].z), "+v"(bv[1].w),
                       "+v"(bv[2].x), "+v"(bv[2].y), "+v"(bv[2].z), "+v"(bv[2].w), "+v"(bv[3].x), "+v"(bv[3].y), "+v"(bv[3].z), "+v"(bv[3].w));
 }
-
-__device__ __forceinline__ float lrelu(float x) { return x > 0.f ? x : 0.2f * x; }   // F.leaky_relu(x, 0.2)
 
 // epilogue constants in LDS (f32): the per-channel vectors and conv4, so that the epilogue's only global reads are the residual's
 constexpr int CST_BIAS = 0, CST_MODW = 256, CST_MODB = 512, CST_PROJW = 768, CST_PROJB = 1536, CST_TOTAL = 1540;
@@ -209,8 +152,8 @@ __global__ __launch_bounds__(256, 1) void conv_f32_kernel(const ConvF32Params p)
                 const int ntap = last ? 0 : (blk + 1 < NB ? tap : tap + 1), nblk = blk + 1 < NB ? blk + 1 : 0;
                 inside = load_b<TAPS, CIN>(p.in, p.H, p.W, last ? nq.y : q.y, last ? nq.x : q.x, last ? nq.ok : q.ok, ntap, nblk, h, bv);
                 chunk_fetch(p.wpk, (blk & 1) ? wb0 : wb1, ntap * NB + nblk, wave, lane16);
-                if constexpr (TAPS > 1) chunk_mul8((blk & 1) ? wb1 : wb0, lane, b, acc);
-                else chunk_mul8((blk & 1) ? wb1 : wb0, lane, b, tot);
+                if constexpr (TAPS > 1) chunk_mul8_ahead((blk & 1) ? wb1 : wb0, lane, b, acc);
+                else chunk_mul8_ahead((blk & 1) ? wb1 : wb0, lane, b, tot);
                 __syncthreads();
                 // (the loaded values are not touched before the barrier: hipcc would otherwise select the zeros, or copy the
                 //  registers, right behind the loads -- in the middle of this chunk's MFMAs -- and wait for them there)
@@ -296,8 +239,8 @@ __global__ __launch_bounds__(256) void pack_conv_f32_kernel(const float *w_oihw,
     const int nb = cin / 32;
     const int cp = (int)(g / CHUNK_FLOATS), rem = (int)(g % CHUNK_FLOATS);
     const int tap = cp / nb, blk = cp % nb;
-    const int kk = rem / 512, in = rem % 512, ib = 4 * (in / 256) + (in & 3), lane = (in % 256) / 4, h = lane >> 5, row = 32 * ib + (lane & 31);
-    out[g] = w_oihw[((size_t)row * cin + 32 * blk + 16 * h + kk) * taps + tap];
+    const ChunkPos s = chunk_pos8(rem);
+    out[g] = w_oihw[((size_t)s.row * cin + 32 * blk + 16 * s.h + s.kk) * taps + tap];
 }
 
 bool supported(int cin, int taps) { return (taps == 9 && cin == 256) || (taps == 1 && (cin == 256 || cin == 64)); }

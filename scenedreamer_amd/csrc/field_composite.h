@@ -1,7 +1,8 @@
-// What the field kernels do around their MLP, once: the LDS prologue, LightningMLP's (sigma, c) row store, the volume
-// rendering of mc_utils.volum_rendering_relu (mc_utils.py:154-161) over the quad of lanes that holds a ray's 4 samples of a
-// pass, and Generator._forward_perpix's sky compositing (scenedreamer.py:373-413), plus the launch helpers of their entry
-// points.  Shared by the f16-split kernels (field.hip: mlp_kernel, every mode) and the fp32 kernel (field_f32.hip), which
+// What the field kernels do around their MLP, once: the LDS prologue, the volume rendering of mc_utils.volum_rendering_relu
+// (mc_utils.py:154-161) over the quad of lanes that holds a ray's 4 samples of a pass, and Generator._forward_perpix's sky
+// compositing (scenedreamer.py:373-413), plus the launch helpers of their entry points (LightningMLP's (sigma, c) row store,
+// store_colour_row, is mlp_layers.h's: the fp32 sky kernel stores its rows with it too).
+// Shared by the f16-split kernels (field.hip: mlp_kernel, every mode) and the fp32 kernel (field_f32.hip), which
 // differ in how a pass computes (sigma, col) and in nothing else: both leave sigma per lane (sample j = lane & 31, both lane
 // halves) and col[ib][r] = colour feature 32 ib + 8 (r / 4) + 4 h + r % 4 of that sample.  A lane's quad (q = lane & 3) is
 // one ray.  All of it is per translation unit (anonymous namespace / static), like field_enc.h, which it sits on.
@@ -30,16 +31,6 @@ __device__ __forceinline__ void stage_enc_tables(EncParams &enc, const EncParams
     if (cam_ori_dev) {   // (uniform: three scalar loads)
         enc.ori[0] = cam_ori_dev[0]; enc.ori[1] = cam_ori_dev[1]; enc.ori[2] = cam_ori_dev[2];
     }
-}
-
-// ---- a sample's 64 colour features -> dst[0 .. 63] (fc_out_c's output, layers.py:124) ----------------------------------------------
-__device__ __forceinline__ void store_colour_row(float *dst, const f32x16 (&col)[2], int h) {
-#pragma unroll
-    for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; g4++)   // registers 4 g4 .. 4 g4 + 3 of row block ib = features 32 ib + 8 g4 + 4 h + e
-            *reinterpret_cast<float4 *>(dst + 32 * ib + 8 * g4 + 4 * h) =
-                make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
 }
 
 // ---- volume rendering (mc_utils.py:154-161) over the 4 samples of each ray in this pass: the weight of this lane's sample.

@@ -19,19 +19,13 @@
 //   field_f32_kernel<RAW>     rows x [n,128] + label u8 [n] -> sigma [n], c [n,64].
 //   pack_f32_kernel           the folded weights in the order the kernel consumes them.
 //
-// Layout.  The MLP is evaluated transposed, W as the A operand (32 output channels per block), the 32 samples as columns.
-// Lane l = (h = l >> 5, j = l & 31) holds A[i = j][k = h] and B[k = h][col j], one f32 each; accumulator register r of
-// lane (h, j) holds channel 8 (r / 4) + 4 h + r % 4 of sample j.  The packed weights order the k-steps of every hidden layer
-// so that k-step r of input block b pairs channels 32 b + 8 (r / 4) + r % 4 (h = 0) and ... + 4 (h = 1): accumulator
-// register r of block b, after bias + LeakyReLU, IS the B operand of that k-step.  Activations never leave the registers
-// and never cross lanes.  The encode stage feeds fc_1 the same way: lane (h, j) blends levels 2 s + h, k-step (s, c) takes
-// channel c of that level from it.
-// Weights: 46 chunks of 32 KiB per pass (4 fc_1, 8 per hidden layer, 2 fc_out_c), the same for every pass.  The four waves
-// share one copy: chunk n + 1 is copied L2 -> LDS (global_load_lds, 16 B per lane, lane-linear image) into the second
-// buffer while chunk n is multiplied; one __syncthreads() per chunk (128 MFMAs of 64 cycles per wave) ends both.
-// What is not the MLP -- the LDS prologue, the (sigma, c) row store, volume rendering, sky compositing, the launch helpers -- is
-// field_composite.h, shared with field.hip; the layer code (chunk_fetch, chunk_mul8, activate, chunk_out2) is mlp_f32.h, shared with
-// sky_f32.hip; the kernel owns its LDS layout, its pass loop and the ray index it derives again for the epilogue.
+// Lanes, streams and the chunk pipeline are mlp_f32.h's (the one statement of the layout).  What is the field's own: the encode stage
+// feeds fc_1 the way a layer feeds the next -- lane (h, j) blends levels 2 s + h, k-step (s, c) takes channel c of that level from
+// it -- and the stream is 46 chunks per pass (4 fc_1, 8 per hidden layer, 2 fc_out_c), the same for every pass.
+// What is not the MLP -- the LDS prologue, volume rendering, sky compositing, the launch helpers -- is field_composite.h, shared with
+// field.hip (the (sigma, c) row store is mlp_layers.h's); the layer code (hidden_layer, out_layer and the chunk primitives under them) is mlp_f32.h,
+// shared with sky_f32.hip and cnn_f32.hip; the kernel owns its LDS layout, its pass loop and the ray index it derives again for the
+// epilogue.
 #include <type_traits>
 
 #include "field_composite.h"
@@ -85,6 +79,7 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, j = lane & 31, q = j & 3;
     const unsigned lane16 = lane * 16;
+    const WeightBuffers ws{p.wpk, wb0, wb1, wave, lane, lane16};
 
     chunk_fetch(p.wpk, wb0, 0, wave, lane16);
     float *cst = reinterpret_cast<float *>(lds + F32_LDS_CONST);
@@ -176,12 +171,7 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
             float part = 0.f;
 #pragma unroll 1
             for (int l = 0; l < 5; l++) {
-#pragma unroll
-                for (int b = 0; b < 8; b++) {
-                    chunk_fetch(p.wpk, (b & 1) ? wb0 : wb1, 4 + 8 * l + b + 1, wave, lane16);
-                    chunk_mul8((b & 1) ? wb1 : wb0, lane, act[b], acc);
-                    __syncthreads();
-                }
+                hidden_layer(ws, 4 + 8 * l, act, acc);
                 activate(acc, cst + C_BETA + l * HID, h, act);
                 if (l == 2) {   // fc_sigma on fc_4's activations (layers.py:115): this lane's 128 channels, then the other half's
                     const float *wsig = cst + C_WSIGMA;
@@ -197,23 +187,9 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
                         }
                 }
             }
-            // ---- fc_out_c: chunks 44, 45 = input blocks 0-3, 4-7; a k-step is [lane][2 output blocks] ----------------------------
+            // ---- fc_out_c: chunks 44, 45, and chunk 0 of the next pass behind them ------------------------------------------------------
             f32x16 col[2];
-            col[0] = zero16();
-            col[1] = zero16();
-            chunk_fetch(p.wpk, wb1, N_CHUNKS - 1, wave, lane16);
-            chunk_out2<0>(wb0, lane, act, col);
-            __syncthreads();
-            chunk_fetch(p.wpk, wb0, 0, wave, lane16);   // (chunk 0 of the next pass)
-            chunk_out2<1>(wb1, lane, act, col);
-            __syncthreads();
-#pragma unroll
-            for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const float4 bv = *reinterpret_cast<const float4 *>(cst + C_BC + 32 * ib + 8 * g + 4 * h);
-                    col[ib][4 * g + 0] += bv.x; col[ib][4 * g + 1] += bv.y; col[ib][4 * g + 2] += bv.z; col[ib][4 * g + 3] += bv.w;
-                }
+            out_layer(ws, N_CHUNKS - 2, 0, act, cst + C_BC, h, col);
             const float sigma = part + __shfl_xor(part, 32) + cst[C_BSIGMA];
             if constexpr (RAW) {   // LightningMLP.forward's outputs for this lane's row: (sigma, c), layers.py:115, :125
                 if (tile_ok && row < p.R) {
@@ -261,14 +237,9 @@ __global__ __launch_bounds__(256, 1) void field_f32_kernel(const F32Params p) {
 }
 
 // ---- the packed stream --------------------------------------------------------------------------------------------------------
-struct PackF32Params {
-    const float *w1;      // [256,128]
-    const float *wh[5];   // [256,256] each, W * alpha already folded
-    const float *wc;      // [64,256]
-    float *out;
-};
-
-__global__ __launch_bounds__(256) void pack_f32_kernel(const PackF32Params p) {
+// The decodes are chunk_pos8 / chunk_pos2 / mlp_stream_weight (mlp_f32.h) spelled out: called, they cost this kernel a register (9 -> 10
+// or 11 VGPRs, profiles/f32_layer_refactor.md).  tests/test_f32_pack_gpu.py holds it to the same layout as the other two pack kernels.
+__global__ __launch_bounds__(256) void pack_f32_kernel(const MlpPackF32<5> p) {   // wh: W * alpha already folded
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;   // one thread per float of the stream
     if (g >= PACKED_F32_FLOATS) return;
     const int cp = (int)(g / CHUNK_FLOATS), rem = (int)(g % CHUNK_FLOATS);
@@ -292,17 +263,7 @@ size_t sdn_field_f32_packed_weight_bytes(void) { return PACKED_F32_FLOATS * size
 size_t sdn_field_f32_consts_floats(void) { return C_TOTAL; }
 
 int sdn_field_pack_weights_f32(const float *w1, const float *const *wh5_host, const float *wc, void *packed, sdn_stream_t stream) {
-    SDN_REQUIRE(w1 && wh5_host && wc && packed, "sdn_field_pack_weights_f32: null pointer");
-    PackF32Params p;
-    p.w1 = w1;
-    for (int i = 0; i < 5; i++) {
-        SDN_REQUIRE(wh5_host[i], "sdn_field_pack_weights_f32: null hidden weight");
-        p.wh[i] = wh5_host[i];
-    }
-    p.wc = wc;
-    p.out = (float *)packed;
-    hipLaunchKernelGGL(pack_f32_kernel, dim3((unsigned)sdn::div_up<size_t>(PACKED_F32_FLOATS, 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return sdn::check_launch("sdn_field_pack_weights_f32");
+    return pack_mlp_weights_f32<5>("sdn_field_pack_weights_f32", pack_f32_kernel, PACKED_F32_FLOATS, w1, wh5_host, wc, packed, stream);
 }
 
 // the two field entries: argument checks, parameter fill, launch.  `stochastic`: the entry accepts u_dev

@@ -136,6 +136,16 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 
+// a row's 64 output features -> dst[0 .. 63]: fc_out_c's accumulators (layers.py:124, gancraft_base.py:168), f16 and fp32 kernels alike
+__device__ __forceinline__ void store_colour_row(float *dst, const f32x16 (&col)[2], int h) {
+#pragma unroll
+    for (int ib = 0; ib < 2; ib++)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; g4++)   // registers 4 g4 .. 4 g4 + 3 of row block ib = features 32 ib + 8 g4 + 4 h + e
+            *reinterpret_cast<float4 *>(dst + 32 * ib + 8 * g4 + 4 * h) =
+                make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
+}
+
 struct Ring {
     int slots_per_pass;   // 92 for the field MLP, 72 for the sky MLP
     const char *wbytes;   // packed weights

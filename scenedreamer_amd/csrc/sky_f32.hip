@@ -5,17 +5,14 @@
 // nothing is calibrated, and no bit depends on a library's choice of solver or summation order.  It is the sky of the exact
 // rung (field_f32.hip, cnn_f32.hip), not the default: on weights sky_kernel accepts it is no closer to fp64 than sky_kernel is.
 //
-//   sky_f32_kernel<PRE>    32 rays per wave as the 32 columns of the B operand (the lane layout of mlp_f32.h), 4 waves = a 128-ray
+//   sky_f32_kernel<PRE>    32 rays per wave as the 32 columns of the B operand (lanes, streams and chunk pipeline: mlp_f32.h), 4 waves = a 128-ray
 //                          group per workgroup, groups grid-strided.  fc1 + style bias -> fc2 .. fc5 -> fc_out_c; activations stay
 //                          in registers.  PRE = false: ray directions [n,3], encoded here by posenc_enc.h (the op's own function);
 //                          PRE = true: SKYMLP.forward's argument [n,33].  Both give the same bits on the op's encoding.
 //   sky_pack_f32_kernel    every weight once, in the order the kernel consumes them.
 //
-// Weights: 36 chunks of 32 KiB per group (2 fc1, 8 per hidden layer, 2 fc_out_c), double-buffered through two LDS objects by
-// global_load_lds, one __syncthreads() per chunk (128 MFMAs of 64 cycles per wave), as in field_f32.hip.
-// fc1 has K = 33: it is padded to K = 64, TWO full chunks, with zero weights and zero inputs (fmaf(0, 0, acc) is acc: exact).
-// k-step t of fc1 pairs encoded elements 2 t (h = 0) and 2 t + 1 (h = 1), so chunk 0 holds elements 0 .. 31 and chunk 1 element
-// 32 and 31 zeros.  Cost: 256 MFMAs for fc1 where 17 k-steps x 8 blocks = 136 would do, 120 of 4608 = 2.6 % of the matrix issue
+// Weights: 36 chunks per group (2 fc1, 8 per hidden layer, 2 fc_out_c).  fc1 has K = 33: it is padded to K = 64, TWO full chunks,
+// with zero weights and zero inputs (fmaf(0, 0, acc) is acc: exact).  Cost: 256 MFMAs for fc1 where 17 k-steps x 8 blocks = 136 would do, 120 of 4608 = 2.6 % of the matrix issue
 // (arithmetic).  One chunk plus a one-k-step tail would save them, for a 34 KiB chunk that does not fit the 32 KiB buffers or a
 // second kind of fetch; the uniform chunk loop was kept.
 // Frame mean: the 32 rays of a tile are added in f32 as a depth-5 tree (the DPP / __shfl_xor sequence of sky_kernel); every
@@ -65,6 +62,7 @@ __global__ __launch_bounds__(256, 1) void sky_f32_kernel(const SkyF32Params p) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, j = lane & 31, q = j & 3;
     const unsigned lane16 = lane * 16;
+    const WeightBuffers ws{p.wpk, wb0, wb1, wave, lane, lane16};
 
     chunk_fetch(p.wpk, wb0, 0, wave, lane16);
     for (int i = threadIdx.x; i < SC_TOTAL; i += 256) cst[i] = p.consts[i];
@@ -125,40 +123,13 @@ __global__ __launch_bounds__(256, 1) void sky_f32_kernel(const SkyF32Params p) {
         // ---- fc2 .. fc5: chunks 2 + 8 l + b, b = input block -----------------------------------------------------------------------
 #pragma unroll 1
         for (int l = 0; l < 4; l++) {
-#pragma unroll
-            for (int b = 0; b < 8; b++) {
-                chunk_fetch(p.wpk, (b & 1) ? wb0 : wb1, 2 + 8 * l + b + 1, wave, lane16);
-                chunk_mul8((b & 1) ? wb1 : wb0, lane, act[b], acc);
-                __syncthreads();
-            }
+            hidden_layer(ws, 2 + 8 * l, act, acc);
             activate(acc, cst + SC_BIASH + l * HID, h, act);
         }
-        // ---- fc_out_c: chunks 34, 35 = input blocks 0-3, 4-7 -----------------------------------------------------------------------
+        // ---- fc_out_c: chunks 34, 35, and chunk 0 of the next group behind them; sky_c[ray] ---------------------------------------------
         f32x16 col[2];
-        col[0] = zero16();
-        col[1] = zero16();
-        chunk_fetch(p.wpk, wb1, SKY_F32_CHUNKS - 1, wave, lane16);
-        chunk_out2<0>(wb0, lane, act, col);
-        __syncthreads();
-        chunk_fetch(p.wpk, wb0, 0, wave, lane16);       // (chunk 0 of the next group)
-        chunk_out2<1>(wb1, lane, act, col);
-        __syncthreads();
-#pragma unroll
-        for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const float4 bv = *reinterpret_cast<const float4 *>(cst + SC_BC + 32 * ib + 8 * g + 4 * h);
-                col[ib][4 * g + 0] += bv.x; col[ib][4 * g + 1] += bv.y; col[ib][4 * g + 2] += bv.z; col[ib][4 * g + 3] += bv.w;
-            }
-        // ---- store sky_c[ray][feature]; registers 4 g .. 4 g + 3 of block ib = features 32 ib + 8 g + 4 h + e ------------------------
-        if (ray_ok) {
-#pragma unroll
-            for (int ib = 0; ib < 2; ib++)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; g4++)
-                    *reinterpret_cast<float4 *>(p.sky_c + (size_t)ray * OUTC + 32 * ib + 8 * g4 + 4 * h) =
-                        make_float4(col[ib][4 * g4], col[ib][4 * g4 + 1], col[ib][4 * g4 + 2], col[ib][4 * g4 + 3]);
-        }
+        out_layer(ws, SKY_F32_CHUNKS - 2, 0, act, cst + SC_BC, h, col);
+        if (ray_ok) store_colour_row(p.sky_c + (size_t)ray * OUTC, col, h);
         // ---- the tile's 32 rays added in f32, a depth-5 tree (sky_kernel's sequence: quad, half-row mirror, row mirror within a
         //      row of 16 lanes, one exchange for the other row); from here on f64 -------------------------------------------------------
 #pragma unroll
@@ -206,31 +177,13 @@ __global__ __launch_bounds__(256, 1) void sky_f32_kernel(const SkyF32Params p) {
 }
 
 // ---- the packed stream --------------------------------------------------------------------------------------------------------
-struct SkyPackF32Params {
-    const float *w1;      // [256,33]
-    const float *wh[4];   // [256,256] each: fc2 .. fc5
-    const float *wc;      // [64,256]
-    float *out;
-};
-
-__global__ __launch_bounds__(256) void sky_pack_f32_kernel(const SkyPackF32Params p) {
+__global__ __launch_bounds__(256) void sky_pack_f32_kernel(const MlpPackF32<4> p) {   // w1 [256,33]; wh: fc2 .. fc5
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;   // one thread per float of the stream
     if (g >= SKY_F32_FLOATS) return;
-    const int cp = (int)(g / CHUNK_FLOATS), rem = (int)(g % CHUNK_FLOATS);
-    float v;
-    if (cp < SKY_F32_CHUNKS - 2) {   // an 8-block chunk (chunk_mul8)
-        const int kk = rem / 512, in = rem % 512, ib = 4 * (in / 256) + (in & 3), lane = (in % 256) / 4, h = lane >> 5, row = 32 * ib + (lane & 31);
-        if (cp < 2) {
-            const int k = 2 * (16 * cp + kk) + h;
-            v = k < SKY_IN ? p.w1[(size_t)row * SKY_IN + k] : 0.f;
-        } else {
-            v = p.wh[(cp - 2) / 8][(size_t)row * HID + 32 * ((cp - 2) % 8) + kmap_f32(kk, h)];
-        }
-    } else {                         // a chunk of the 2-block output layer (chunk_out2)
-        const int kk = rem / 128, in = rem % 128, ib = in & 1, lane = in / 2, h = lane >> 5, row = 32 * ib + (lane & 31);
-        v = p.wc[(size_t)row * HID + 32 * (4 * (cp - (SKY_F32_CHUNKS - 2)) + (kk >> 4)) + kmap_f32(kk & 15, h)];
-    }
-    p.out[g] = v;
+    p.out[g] = mlp_stream_weight<2>(p, g, [&](int cp, ChunkPos s) {
+        const int k = 2 * (16 * cp + s.kk) + s.h;
+        return k < SKY_IN ? p.w1[(size_t)s.row * SKY_IN + k] : 0.f;
+    });
 }
 
 int sky_f32_workgroups(int32_t n_rays, int32_t n_workgroups) {
@@ -246,17 +199,7 @@ extern "C" {
 size_t sdn_sky_f32_packed_weight_bytes(void) { return SKY_F32_FLOATS * sizeof(float); }
 
 int sdn_sky_pack_weights_f32(const float *w1, const float *const *wh4_host, const float *wc, void *packed, sdn_stream_t stream) {
-    SDN_REQUIRE(w1 && wh4_host && wc && packed, "sdn_sky_pack_weights_f32: null pointer");
-    SkyPackF32Params p;
-    p.w1 = w1;
-    for (int i = 0; i < 4; i++) {
-        SDN_REQUIRE(wh4_host[i], "sdn_sky_pack_weights_f32: null hidden weight");
-        p.wh[i] = wh4_host[i];
-    }
-    p.wc = wc;
-    p.out = (float *)packed;
-    hipLaunchKernelGGL(sky_pack_f32_kernel, dim3((unsigned)sdn::div_up<size_t>(SKY_F32_FLOATS, 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return sdn::check_launch("sdn_sky_pack_weights_f32");
+    return pack_mlp_weights_f32<4>("sdn_sky_pack_weights_f32", sky_pack_f32_kernel, SKY_F32_FLOATS, w1, wh4_host, wc, packed, stream);
 }
 
 int32_t sdn_sky_f32_partial_rows(int32_t n_rays, int32_t n_workgroups) { return n_rays > 0 ? 4 * sky_f32_workgroups(n_rays, n_workgroups) : 0; }
