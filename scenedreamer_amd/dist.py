@@ -351,10 +351,7 @@ def agree_precision(renderer, pose, resolution_hw, num_samples, group=None, more
     the middle pose of its trajectory (Renderer.calibrate_style) -- the same policy, so a multi-rank job cannot adopt a cheaper
     rung than one process would for the same style and trajectory.  What a closed gate selects is Renderer.fallback ("unfused" or
     "exact"), read by adopt_precision after the reduction: every rank must have been given the same value.  Returns {"cnn": cnn_calibration, "field": field_gate}."""
-    renderer.cnn_calibration = None
-    renderer.field_gate = None
-    renderer.colour_terms_auto = None
-    renderer.sky_terms_auto = None
+    renderer.reset_gates(cnn=True)       # every gate is decided afresh for the job; the packed CNN forms stay
     meas = renderer.calibrate_style(pose, resolution_hw, num_samples, more_poses=more_poses)["measurements"]
     if _is_init() and dist.get_world_size(group) > 1:
         world = dist.get_world_size(group)

@@ -8,6 +8,8 @@ import numpy as np
 import torch
 
 from . import capi
+from .precision import TERM_EPS_DEFAULT      # noqa: F401  (the default of term_eps, named here by callers)
+from .timing import _time_ms
 
 _f2 = ctypes.c_float * 2
 _f3 = ctypes.c_float * 3
@@ -193,7 +195,7 @@ def prepare_style_f32(R):
 def _lin(R, ns, stratified=False):
     """The stratified points' positions on the device, cached per renderer: deterministic linspace(0, 1, ns + 3)[1:-1]
     (mc_utils.py:120), or the training-time sampling's linspace(0, 1, ns + 2)[:-1] (mc_utils.py:124)."""
-    buf = R.__dict__.setdefault("_fused_lin", {})
+    buf = R._cache("_fused_lin")
     key = ("strat" if stratified else "det", ns)
     lin = buf.get(key)
     if lin is None:
@@ -246,7 +248,7 @@ def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None, u=None
     kernel's FIELD_AUX instantiation).  net_out [window.n_rays, 64] in the window's row-major order, like every aux array.
     With u None and aux None the call is sdn_field_render_f32, as it was before either existed."""
     sc = R._fused_scene or prepare_scene(R)
-    st = getattr(R, "_fused_style_f32", None) or prepare_style_f32(R)
+    st = R._fused_style_f32 or prepare_style_f32(R)
     if window is None:
         window = Window(vid.shape[0])
     n_rays = window.n_rays
@@ -285,7 +287,7 @@ def field_exact(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, window=None, u=None
 
 def render_mlp_exact(R, x, label):
     """LightningMLP.forward for rows x [n,128] f32 and labels u8 [n] by the fp32 kernel: (sigma [n], c [n,64])."""
-    st = getattr(R, "_fused_style_f32", None) or prepare_style_f32(R)
+    st = R._fused_style_f32 or prepare_style_f32(R)
     x, label = x.contiguous(), label.contiguous()
     n = x.shape[0]
     assert x.dtype == torch.float32 and tuple(x.shape) == (n, 128) and label.dtype == torch.uint8 and label.numel() == n
@@ -301,7 +303,7 @@ def render_mlp_exact(R, x, label):
 
 def _buffers(R, n_rays, ns, slot=0):
     key = (n_rays, ns, slot)
-    cache = R.__dict__.setdefault("_fused_buf", {})
+    cache = R._cache("_fused_buf")
     if key not in cache:
         lib = _lib()
         while len(cache) >= 4:      # two apron settings x two pipeline slots of one resolution; older shapes are dropped
@@ -361,26 +363,9 @@ def precision_profile(R):
     equal to the full split's to 1e-6 on the goldens, half the MFMA issue slots); 3 = the 3-term f16 split like every other
     layer; 2 = without Whi.Xlo (4-7e-4 on net_out: opt-in only).
     term_eps: early ray termination once the transmittance of all 32 rays of a workgroup is below it (0 = off);
-    bounds the change of net_out by 2 * term_eps.  Default TERM_EPS_DEFAULT (below); set_precision(term_eps=0) / SDN_TERM_EPS=0
+    bounds the change of net_out by 2 * term_eps.  Default precision.TERM_EPS_DEFAULT; set_precision(term_eps=0) / SDN_TERM_EPS=0
     evaluate every sample like the reference."""
-    ct = getattr(R, "colour_terms", None)
-    if ct is None:
-        if "SDN_MLP_COLOUR_TERMS" in os.environ:
-            ct = int(os.environ["SDN_MLP_COLOUR_TERMS"])
-        else:       # the per-style decision of Renderer.calibrate_field (6 unless the fp6 corrections cost more than its bound)
-            ct = getattr(R, "colour_terms_auto", None) or 6
-    eps = getattr(R, "term_eps", None)
-    if eps is None:
-        eps = float(os.environ.get("SDN_TERM_EPS", TERM_EPS_DEFAULT))
-    return ct, eps
-
-
-# Early ray termination is ON by default: a 32-ray group stops sampling once the transmittance of every one of its rays is below
-# this (wavefront ballots, field.hip).  It moves net_out by at most 2 x eps = 1e-4 of the 1e-3 tolerance (typically far less: the
-# bound assumes all of the remaining mass sits in the skipped samples); the renderer's per-style calibration measures the path
-# WITH it, so the charge is inside the measured error.  On the synthetic benchmark weights it removes 2 - 6 % of the field
-# kernel's passes, on an opaque-surface weight set 5 of 6 (tests/test_render_gpu.py, bench.py `early_termination`).
-TERM_EPS_DEFAULT = "5e-5"
+    return R.resolved_colour_terms(), R.resolved_term_eps()
 
 
 def _launch_mlp(R, buf, st, sky_c, sky_avg, net_out, n_rays, ns, passes=None, window=None, ray0=0, dynamic=True):
@@ -416,23 +401,14 @@ def mlp_from(R, buf, sky_c, sky_avg, n_rays, ns, window=None):
 def single_kernel(R):
     """Whether the field runs as ONE kernel (sdn_field_render: every pass gathers its own features) or as encode_kernel +
     mlp_kernel with the features handed over through HBM.  Renderer.field_single_kernel, else SDN_FIELD_SINGLE_KERNEL, else
-    the default below."""
-    v = getattr(R, "field_single_kernel", None)
-    if v is None:
-        v = os.environ.get("SDN_FIELD_SINGLE_KERNEL", SINGLE_KERNEL_DEFAULT) not in ("0", "", "false")
-    return bool(v)
-
-
-SINGLE_KERNEL_DEFAULT = "1"   # same frame time as the two-kernel sequence (A/B, DESIGN.md section 6), without its 10.8 GB/frame of HBM hand-off
+    precision.SINGLE_KERNEL_DEFAULT."""
+    return R.resolved_single_kernel()
 
 
 def colour_skip(R):
     """Whether field_kernel skips the colour branch of passes whose 128 samples all have volume-rendering weight exactly zero
     (csrc/field.hip; bit-identical output).  Renderer.colour_skip, else SDN_COLOUR_SKIP, else on."""
-    v = getattr(R, "colour_skip", None)
-    if v is None:
-        v = os.environ.get("SDN_COLOUR_SKIP", "1") not in ("0", "", "false")
-    return bool(v)
+    return R.resolved_colour_skip()
 
 
 def field_render(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, passes=None, u=None, window=None, division="reciprocal",
@@ -536,7 +512,6 @@ def field_fused(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, passes=None, u=None
 
 def time_mlp_kernel(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, reps=5):
     """(samples per launch, avg ms) of mlp_kernel alone (features already encoded)."""
-    from .renderer import _time_ms
     st = R._fused_style or prepare_style(R)
     n = vid.numel() // R.M
     vid, d2, rd = vid.reshape(n, R.M).contiguous(), d2.reshape(2, n, R.M).contiguous(), rd.reshape(n, 3).contiguous()
@@ -560,7 +535,6 @@ def time_mlp_kernel(R, vid, d2, rd, cam_ori, sky_c, sky_avg, ns, reps=5):
 
 def time_encode_kernel(R, vid, d2, rd, cam_ori, ns, reps=5):
     """(samples per launch, avg ms, algorithmic bytes per sample, kernel name) for the roofline record."""
-    from .renderer import _time_ms
     n = vid.numel() // R.M
     vid, d2, rd = vid.reshape(n, R.M).contiguous(), d2.reshape(2, n, R.M).contiguous(), rd.reshape(n, 3).contiguous()
     buf = _buffers(R, n, ns)
@@ -620,7 +594,7 @@ def sky_exact(R, rd, encoded=False, mean=True, n_workgroups=0):
     rows.  Every product is an f32 x f32 fmaf in a fixed order; the mean is a depth-5 f32 tree over each 32-ray tile, then f64, in
     a fixed order.  The weights need not fit f16 (no TrunkRangeError) and nothing is calibrated.
     mean=False: no frame mean (sky_avg is None), for a band that owns only part of the frame's rays."""
-    sk = getattr(R, "_fused_sky_f32", None) or prepare_sky_exact(R)
+    sk = R._fused_sky_f32 or prepare_sky_exact(R)
     rd = rd.contiguous()
     n = rd.shape[0]
     if not (rd.dim() == 2 and rd.shape[1] == (33 if encoded else 3) and rd.dtype == torch.float32 and rd.is_cuda and rd.device == R.dev and n > 0):
@@ -642,17 +616,14 @@ def sky_terms(R):
     """Products of the sky MLP's hidden layers fc2..fc5: 3 = 3-term f16 split; 6 = f16 Whi.Xhi + block-scaled fp6 corrections (the
     colour layers' scheme: ~15 % less sky time, errors of the four layers stack to ~1e-4 on sky_c).  Renderer.sky_terms, else
     SDN_SKY_TERMS, else the per-style decision of Renderer.calibrate_style (`sky_terms_auto`), else 3."""
-    t = getattr(R, "sky_terms", None)
-    if t is None and "SDN_SKY_TERMS" in os.environ:
-        t = int(os.environ["SDN_SKY_TERMS"])
-    return t or getattr(R, "sky_terms_auto", None) or 3
+    return R.resolved_sky_terms()
 
 
 def sky_fused(R, rd, encoded=False):
     """sky_c [R,64] and the frame mean sky_avg [1,64] for ray directions rd [R,3] (the mean is finished inside the kernel by
     its last workgroup: fixed summation order, no host-side reduction).
     encoded: rd is [R,33], rows that are already positional-encoded (SKYMLP.forward's own argument)."""
-    sk = getattr(R, "_fused_sky", None) or prepare_sky(R)
+    sk = R._fused_sky or prepare_sky(R)
     rd = rd.contiguous()
     n = rd.shape[0]
     assert rd.dim() == 2 and rd.shape[1] == (33 if encoded else 3) and rd.dtype == torch.float32 and rd.device == R.dev

@@ -32,30 +32,24 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import capi
-from .renderer import Renderer, fold_denoiser, fold_render_net, fold_sky_net
+from . import precision as P
+from .renderer import fold_denoiser, fold_render_net, fold_sky_net
 
 
-class Backend:
+class Backend(P.PrecisionState):
     """What fused.* and cnn.MfmaCNN expect of a renderer (`w`: the reference's parameter names -> device tensors, `dev`, the
     per-style constants, the packed-weight caches), fed from LIVE nn.Module parameters: `bind` aliases them, and notices
     in-place updates (load_state_dict, an optimizer step) and re-allocations (.cuda()) through the tensors' version counters
     and addresses, so packed weights are rebuilt exactly when they are stale."""
-    mfma_cnn = Renderer.mfma_cnn
-    f32_cnn = Renderer.f32_cnn
-    _cnn_form = Renderer._cnn_form
-    _drop_other_cnn_planes = Renderer._drop_other_cnn_planes
-    set_precision = Renderer.set_precision
 
     def __init__(self):
         self.dev = None
         self.w = {}
         self.M, self.sample_depth, self.dists_scale, self.pad = 6, 3.0, 0.25, 0
-        self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = self._fused_sky_f32 = None
-        self.cnn_calibration = None
         self._bound = {}
         self._zkey = {}
         self._zref = {}     # the style tensor each _zkey was taken from, kept ALIVE: see style()
-        self.sky_terms_auto = self._sky_gate_key = self.sky_gate = None
+        self._sky_gate_key = self.sky_gate = None
 
     @staticmethod
     def tensors_key(module):
@@ -78,13 +72,13 @@ class Backend:
             self.w = {k: v for k, v in self.w.items() if k.startswith(prefix)}
             self._bound.clear()
             self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = self._fused_sky_f32 = None
-            self.__dict__.pop("_mfma_cnns", None)
+            self._mfma_cnns = None
         self.dev = dev
         self._bound[prefix] = (module, key)
         self._zkey.pop(prefix, None)
         self._zref.pop(prefix, None)
         if prefix == "denoiser.":
-            self.__dict__.pop("_mfma_cnns", None)   # packed convolution weights
+            self._mfma_cnns = None          # packed convolution weights
             self.cnn_calibration = None
         if prefix == "hash_encoder.":
             self._fused_scene = None
@@ -95,9 +89,8 @@ class Backend:
     def _reset_sky_gate(self):
         """The sky MLP's hidden-layer form is a per-style, per-weights MEASUREMENT (SKYMLPNative.forward): new weights or a new
         style start from the 3-term form until it has been re-measured."""
-        self.sky_terms_auto = None
-        self._sky_gate_key = None
-        self.sky_gate = None
+        self.reset_gates()      # (sky_terms_auto: nothing in the package gives a Backend the field's two decisions)
+        self._sky_gate_key = self.sky_gate = None      # the measurement's key and record, which only this surface keeps
 
     def style(self, prefix, z, item, fold):
         """Fold style code z[item] for the network under `prefix` unless that very tensor content was folded already.
@@ -278,17 +271,16 @@ class SKYMLPNative:
                     # hidden layers are evaluated as f16 + fp6 corrections AND as the 3-term split (4e-6 from fp32); the cheap form is
                     # kept for the style if the two stay within SKY_AUTO_BOUND of each other.  One extra launch per style.
                     gate_key = (B._zkey.get("sky_net."), B._bound["sky_net."][1])
-                    if getattr(B, "_sky_gate_key", None) != gate_key and "SDN_SKY_TERMS" not in os.environ and getattr(B, "sky_terms", None) is None:
-                        from .renderer import SKY_AUTO_BOUND
+                    if B._sky_gate_key != gate_key and B.explicit_sky_terms() is None:
                         B.sky_terms_auto = None
                         c3, _ = fused.sky_fused(B, rd)
                         B.sky_terms_auto = 6
                         c6, _ = fused.sky_fused(B, rd)
                         d = float((c6 - c3).abs().max())
-                        if not d <= SKY_AUTO_BOUND:
+                        if not d <= P.SKY_AUTO_BOUND:
                             B.sky_terms_auto = None
                         B._sky_gate_key = gate_key
-                        B.sky_gate = {"hidden_terms": 6 if B.sky_terms_auto == 6 else 3, "max_abs_diff_fp6_vs_3term": d, "bound": SKY_AUTO_BOUND}
+                        B.sky_gate = {"hidden_terms": 6 if B.sky_terms_auto == 6 else 3, "max_abs_diff_fp6_vs_3term": d, "bound": P.SKY_AUTO_BOUND}
                     sky_c, _ = fused.sky_fused(B, rd)
                     # (rd_ref keeps the ray-direction storage alive: while this record exists its address cannot be handed to
                     #  another tensor, so "same address + same version counter" below means "same content")

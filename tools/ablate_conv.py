@@ -5,7 +5,8 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scenedreamer_amd import synth
-from scenedreamer_amd.renderer import Renderer, _time_ms
+from scenedreamer_amd.renderer import Renderer
+from scenedreamer_amd.timing import _time_ms
 from scenedreamer_amd.cnn import MfmaCNN
 dev = torch.device("cuda:0")
 scene = synth.make_scene(256, 3407, device=dev)

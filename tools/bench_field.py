@@ -8,7 +8,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scenedreamer_amd import camera, fused, synth  # noqa: E402
-from scenedreamer_amd.renderer import Renderer, _time_ms  # noqa: E402
+from scenedreamer_amd.renderer import Renderer  # noqa: E402
+from scenedreamer_amd.timing import _time_ms  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 S = int(os.environ.get("SDN_SCENE", "2048"))

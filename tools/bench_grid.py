@@ -3,7 +3,7 @@ import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scenedreamer_amd import ops, synth
-from scenedreamer_amd.renderer import _time_ms
+from scenedreamer_amd.timing import _time_ms
 w = synth.make_weights(0)
 emb = w["hash_encoder.embeddings"].cuda() if isinstance(w["hash_encoder.embeddings"], torch.Tensor) else torch.as_tensor(np.asarray(w["hash_encoder.embeddings"])).cuda()
 offs = torch.as_tensor(np.asarray(w["hash_encoder.offsets"])).cuda()

@@ -4,7 +4,7 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scenedreamer_amd import camera, ops, synth
-from scenedreamer_amd.renderer import _time_ms
+from scenedreamer_amd.timing import _time_ms
 dev = torch.device("cuda:0")
 scene = synth.make_scene(2048, 3407, device=dev)
 poses = camera.eval_camera_poses(scene, maxstep=40)

@@ -5,7 +5,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from conftest import golden
 from scenedreamer_amd import fused, synth
-from scenedreamer_amd.renderer import Renderer, _time_ms
+from scenedreamer_amd.renderer import Renderer
+from scenedreamer_amd.timing import _time_ms
 g = golden("field_a.npz")
 scene = synth.make_scene(256, 3407, device="cuda")
 R = Renderer(synth.make_weights(0), scene, "cuda")

@@ -76,7 +76,7 @@ def _summary(new, old):
 def step_field(reps, warmup):
     torch, R, pose = _setup()
     from scenedreamer_amd import fused
-    from scenedreamer_amd.renderer import CNN_HALO
+    from scenedreamer_amd.precision import CNN_HALO
     with torch.no_grad():
         vid, d2, rd, (Hp, Wp) = R.cast_rays(pose, HW)
         n = Hp * Wp
@@ -159,7 +159,7 @@ def step_cnn(reps, warmup):
 def step_sky(reps, warmup):
     torch, R, pose = _setup()
     from scenedreamer_amd import fused
-    from scenedreamer_amd.renderer import CNN_HALO
+    from scenedreamer_amd.precision import CNN_HALO
     with torch.no_grad():
         _, _, rd, (Hp, Wp) = R.cast_rays(pose, HW)
         o = R.pad // 2 - CNN_HALO

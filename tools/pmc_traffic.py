@@ -56,7 +56,7 @@ def main(fetch_db, write_db, mfma_db, commit, fetch2_db=None, write2_db=None):
     m_rows, m_dur = counters(mfma_db)
     from scenedreamer_amd import build
     out = {"commit": commit,
-           "csrc_digest": build._digest(),    # renderer._profiled_traffic() refuses this profile once the kernel sources change
+           "csrc_digest": build._digest(),    # roofline._profiled_traffic() refuses this profile once the kernel sources change
            "source": "rocprofv3 --kernel-trace --pmc <one counter set per pass> on tools/frame_once.py fused 3 (frames of poses 0, 2, 4 of "
                      "the headline config, field / CNN on the 4-px apron), tools/prof_round.sh; summarised by tools/pmc_traffic.py",
            "correction": "KiB -> bytes; FETCH_SIZE x2 for 16 B/lane streaming readers (mlp_kernel on the feature buffer, conv_kernel, "
