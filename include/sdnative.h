@@ -463,6 +463,41 @@ int32_t sdn_sky_f32_partial_rows(int32_t n_rays, int32_t n_workgroups);      /* 
 int sdn_sky_mlp_f32(const float *raydirs, const void *packed, const float *consts, float *sky_c, double *sky_partial,
                     int32_t n_rays, int32_t n_workgroups, float *sky_avg, uint32_t *counter, int32_t encoded, sdn_stream_t stream);
 
+/* The world encoder in plain fp32 with a fixed summation order (csrc/world_f32.hip): ConditionalHashGrid.forward
+ * (imaginaire/model_utils/layers.py:40-55) and its five SRTConvBlocks (layers.py:6-23), the F.conv2d calls of which no longer go
+ * through a library's solver choice.  Activations are f32 rows [H*W][channels], channels last.  In every conv and head layer a
+ * tap's products accumulate from zero as an fmaf chain over the input channels in ascending order and the nine tap sums are added
+ * in f32 in the order ky, kx; no bit depends on n_workgroups (<= 0: a default), the process or the device's schedule.
+ *
+ * sdn_wenc_head_f32 replaces layers.py:41-43: hconv_head (wh dev [8,1,3,3], bh dev [8]) on height dev f32 [1,1,H,W] and sconv_head
+ *   (ws dev [8,11,3,3], bs dev [8]) on semantic dev f32 [1,11,H,W] (any f32 values): 3x3, stride 2, zero padding 1, bias,
+ *   LeakyReLU(0.2); out_rows dev f32 [Ho*Wo][16], h in channels 0-7, s in 8-15 (torch.cat([h, s], 1)); Ho = (H - 1) / 2 + 1.
+ * sdn_wenc_conv_f32 replaces one nn.Conv2d + ReLU of layers.py:15-20 (3x3, zero padding 1, no bias; the outer LeakyReLU of :47
+ *   after a ReLU is the identity) on v_mfma_f32_32x32x2_f32: (cin, cout, stride) one of (c, c, 1), (c, 2c, 2), c in {16, 32, 64,
+ *   128, 256}, anything else SDN_ERR_UNSUPPORTED (sdn_wenc_f32_packed_weight_bytes: 0).  in_rows dev [H*W][cin] -> out_rows dev
+ *   [Ho*Wo][cout], Ho = H for stride 1, (H - 1) / 2 + 1 for stride 2; out_rows must not be in_rows (SDN_ERR_UNSUPPORTED).
+ * sdn_wenc_pack_weights_f32: w_oihw dev f32 [cout,cin,3,3] -> packed dev, every weight once, zeros as padding.
+ * sdn_wenc_tail_f32 replaces layers.py:51-54: rows dev [P][512] -> per channel the rows added in row order in f64, / P in f64,
+ *   rounded to f32 (pooled dev f32 [512], or NULL); fc1 (dev [16,512], [16]) and fc2 (dev [2,16], [2]) accumulate in f64 in k
+ *   order, round to f32, add the bias in f32; LeakyReLU(0.2), then tanh evaluated in f64 -> global_enc dev f32 [2].  One workgroup.
+ * SDN_ERR_INVALID for null pointers, H * W < 1 or not below 2^31 - 256, P < 1. */
+size_t sdn_wenc_f32_packed_weight_bytes(int cin, int cout);      /* >= 4*9*cin*cout; 0: unsupported pair */
+int sdn_wenc_pack_weights_f32(const float *w_oihw, int cin, int cout, void *packed, sdn_stream_t stream);
+int sdn_wenc_head_f32(const float *height, const float *semantic, const float *wh, const float *bh, const float *ws, const float *bs,
+                      float *out_rows, int H, int W, int n_workgroups, sdn_stream_t stream);
+int sdn_wenc_conv_f32(const float *in_rows, int cin, int cout, int stride, const void *packed, float *out_rows, int H, int W,
+                      int n_workgroups, sdn_stream_t stream);
+int sdn_wenc_tail_f32(const float *rows, int P, const float *fc1_w, const float *fc1_b, const float *fc2_w, const float *fc2_b,
+                      float *pooled, float *global_enc, sdn_stream_t stream);
+
+/* The style MLP with a fixed summation order (csrc/world_f32.hip), replacing StyleMLP.forward (imaginaire/generators/
+ * gancraft_base.py:113-126; normalize_input, output_act, LeakyReLU(0.2)): style dev f32 [n,128] -> z dev f32 [n,256].
+ * w6_host / b6_host: host arrays of 6 dev pointers, fc_layers.0 ([256,128], [256]), fc_layers.1-4 and fc_out ([256,256], [256]).
+ * F.normalize: sum of squares in f64 in k order, sqrt rounded to f32, max(., 1e-12), a correctly rounded f32 division; every output
+ * of a layer accumulates in f64 in k order, adds its bias in f64 and is rounded to f32 once.  Row i depends on style row i only.
+ * SDN_ERR_INVALID for null pointers (the twelve layer pointers included) and n < 1. */
+int sdn_style_mlp_f32(const float *style, const float *const *w6_host, const float *const *b6_host, float *z, int n, sdn_stream_t stream);
+
 /* test hook: C[32,32] = A[32,16] * B[16,32] through the MFMA operand layouts field.hip relies on */
 int sdn_debug_mfma_probe(const float *A, const float *B, float *C, sdn_stream_t stream);
 

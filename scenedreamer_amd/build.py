@@ -38,6 +38,7 @@ SOURCES = {
     "mlp_pack.hip": MLP_FLAGS,
     "cnn.hip": ABLATION,
     "cnn_f32.hip": ["-fno-slp-vectorize"],
+    "world_f32.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],  # a fixed order: every fused multiply-add is an explicit fmaf
     "scene.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

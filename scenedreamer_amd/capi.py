@@ -99,6 +99,12 @@ _SIGNATURES = {
     "sdn_conv_chain_consts_floats": (ctypes.c_size_t, []),
     "sdn_conv_chain_pack_weights": (c_i, [c_p, c_p, c_p, c_p, c_p]),
     "sdn_conv_chain": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "sdn_wenc_f32_packed_weight_bytes": (ctypes.c_size_t, [c_i, c_i]),
+    "sdn_wenc_pack_weights_f32": (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    "sdn_wenc_head_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "sdn_wenc_conv_f32": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "sdn_wenc_tail_f32": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sdn_style_mlp_f32": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p]),
     "sdn_debug_mfma_probe": (c_i, [c_p, c_p, c_p, c_p]),
 }
 # entry points added by later kernels register themselves here (name -> (restype, argtypes))

@@ -36,6 +36,14 @@ def build_parser():
                     help="render CNN of the exact path (--mode exact, or a closed gate with Renderer.fallback = 'exact'): torch = the "
                          "reference's F.conv2d sequence (default; SDN_EXACT_CNN when not given); f32 = the fp32 MFMA kernel "
                          "(fixed summation order, any weight range).  Every rank of a job must be given the same value")
+    ap.add_argument("--exact-world", dest="exact_world", default=None, choices=["torch", "f32"],
+                    help="world encoder (global_enc, once per scene, in every --mode): torch = the reference's F.conv2d sequence "
+                         "(default; SDN_EXACT_WORLD when not given); f32 = the fixed-order fp32 kernels (no library solver choice "
+                         "between the maps and global_enc).  Every rank of a job must be given the same value")
+    ap.add_argument("--exact-style", dest="exact_style", default=None, choices=["torch", "f32"],
+                    help="style MLP (z, once per style, in every --mode): torch = the reference's F.linear sequence (default; "
+                         "SDN_EXACT_STYLE when not given); f32 = the fixed-order kernel (f64 accumulation in k order).  Every rank of "
+                         "a job must be given the same value")
     ap.add_argument("--exact-sky", dest="exact_sky", default=None, choices=["torch", "f32"],
                     help="sky MLP of the exact path (--mode exact, or a closed gate with Renderer.fallback = 'exact'): torch = the "
                          "reference's F.linear sequence and a library mean (default; SDN_EXACT_SKY when not given); f32 = the fp32 MFMA "
@@ -78,7 +86,7 @@ def main():
         style = synth.make_style(args.seed)                           # inference.py:81-82
     if world > 1:
         scene, weights, style = sdist.broadcast_state(scene, weights, style, dev, src=0)
-    R = Renderer(weights, scene, dev)
+    R = Renderer(weights, scene, dev, exact_world=args.exact_world, exact_style=args.exact_style)
     R.set_style(style)
     if args.exact_cnn is not None:
         R.exact_cnn = args.exact_cnn

@@ -640,3 +640,104 @@ def sky_fused(R, rd, encoded=False):
                                       sky_c.data_ptr(), part.data_ptr(), n, 0, sky_avg.data_ptr(), sk["counter"].data_ptr(),
                                       terms, 1 if encoded else 0, _stream(R.dev)), "sdn_sky_mlp")
     return sky_c, sky_avg
+
+
+# ---- the two networks upstream of every frame, with a fixed summation order (csrc/world_f32.hip) ------------------------------------
+WORLD_PAIRS = tuple((c, c * s, s) for c in (16, 32, 64, 128, 256) for s in (1, 2))     # (cin, cout, stride) of the five SRTConvBlocks
+
+
+def world_layer_names():
+    """The names `world_exact(layers=True)` reports, in evaluation order."""
+    return ["head"] + [f"conv_blocks.{i}.layers.{k}" for i in range(5) for k in (0, 2)]
+
+
+def prepare_world_exact(R):
+    """The world encoder's ten convolution weights in the order wenc_conv_f32_kernel consumes them, and f32 contiguous copies of the
+    head's and the tail's parameters.  Cached as R._fused_world_f32 for the lifetime of R.w's world_encoder entries."""
+    lib = _lib()
+    w = R.w
+    f = lambda n: w["world_encoder." + n].detach().to(torch.float32).contiguous()
+    packed = []
+    with torch.cuda.device(R.dev):
+        for n, (cin, cout, _) in zip(world_layer_names()[1:], WORLD_PAIRS):
+            wt = f(n + ".weight")
+            if tuple(wt.shape) != (cout, cin, 3, 3):
+                raise ValueError(f"world_exact: world_encoder.{n}.weight is {tuple(wt.shape)}, not {(cout, cin, 3, 3)}")
+            buf = torch.empty(lib.sdn_wenc_f32_packed_weight_bytes(cin, cout), dtype=torch.uint8, device=R.dev)
+            capi.check(lib.sdn_wenc_pack_weights_f32(wt.data_ptr(), cin, cout, buf.data_ptr(), _stream(R.dev)), "sdn_wenc_pack_weights_f32")
+            packed.append(buf)
+    head = tuple(f(n) for n in ("hconv_head.weight", "hconv_head.bias", "sconv_head.weight", "sconv_head.bias"))
+    tail = tuple(f(n) for n in ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"))
+    if [tuple(t.shape) for t in head + tail] != [(8, 1, 3, 3), (8,), (8, 11, 3, 3), (8,), (16, 512), (16,), (2, 16), (2,)]:
+        raise ValueError("world_exact: needs the reference's ConditionalHashGrid sizes (1 + 11 -> 8 + 8 head, fc1 512 -> 16, fc2 16 -> 2)")
+    R._fused_world_f32 = dict(packed=packed, head=head, tail=tail)
+    return R._fused_world_f32
+
+
+def world_exact(R, height_map, semantic_map, layers=False, n_workgroups=0):
+    """ConditionalHashGrid.forward (layers.py:40-55) on the fixed-order fp32 kernels: height_map [1,1,H,W], semantic_map [1,11,H,W]
+    -> global_enc [1,2].  layers=True: also {name: rows [Ho*Wo, C]} for every layer (world_layer_names()) plus "pooled" [512].
+    The result is a function of the weights and the maps only: not of n_workgroups, the process, or a library's solver choice.
+    Scratch: two ping-pong row buffers sized by the largest layer, freed on return."""
+    lib = _lib()
+    wx = getattr(R, "_fused_world_f32", None) or prepare_world_exact(R)
+    hm = torch.as_tensor(height_map).to(device=R.dev, dtype=torch.float32).contiguous()
+    sm = torch.as_tensor(semantic_map).to(device=R.dev, dtype=torch.float32).contiguous()
+    if not (hm.dim() == 4 and sm.dim() == 4 and tuple(hm.shape[:2]) == (1, 1) and tuple(sm.shape[:2]) == (1, 11) and
+            hm.shape[2:] == sm.shape[2:] and hm.numel() > 0 and R.dev.type == "cuda"):
+        raise ValueError(f"world_exact: needs height_map [1,1,H,W] and semantic_map [1,11,H,W] on a CUDA device, H, W >= 1 "
+                         f"(got {tuple(hm.shape)}, {tuple(sm.shape)})")
+    H, W = int(hm.shape[2]), int(hm.shape[3])
+    half = lambda v: (v - 1) // 2 + 1
+    h, w = half(H), half(W)
+    largest, hh, ww = h * w * 16, h, w          # the largest layer: the head's on big maps, a late 1x1 x 512 one on tiny maps
+    for _, cout, stride in WORLD_PAIRS:
+        hh, ww = (half(hh), half(ww)) if stride == 2 else (hh, ww)
+        largest = max(largest, hh * ww * cout)
+    bufs = [torch.empty(largest, dtype=torch.float32, device=R.dev) for _ in range(2)]
+    kept = {}
+    st = _stream(R.dev)
+    with torch.cuda.device(R.dev):
+        capi.check(lib.sdn_wenc_head_f32(hm.data_ptr(), sm.data_ptr(), *[t.data_ptr() for t in wx["head"]], bufs[0].data_ptr(), H, W,
+                                         n_workgroups, st), "sdn_wenc_head_f32")
+        if layers:
+            kept["head"] = bufs[0][:h * w * 16].view(h * w, 16).clone()
+        cur = 0
+        for name, pk, (cin, cout, stride) in zip(world_layer_names()[1:], wx["packed"], WORLD_PAIRS):
+            capi.check(lib.sdn_wenc_conv_f32(bufs[cur].data_ptr(), cin, cout, stride, pk.data_ptr(), bufs[1 - cur].data_ptr(), h, w,
+                                             n_workgroups, st), "sdn_wenc_conv_f32")
+            if stride == 2:
+                h, w = half(h), half(w)
+            cur = 1 - cur
+            if layers:
+                kept[name] = bufs[cur][:h * w * cout].view(h * w, cout).clone()
+        genc = torch.empty((1, 2), dtype=torch.float32, device=R.dev)
+        pooled = torch.empty(512, dtype=torch.float32, device=R.dev) if layers else None
+        capi.check(lib.sdn_wenc_tail_f32(bufs[cur].data_ptr(), h * w, *[t.data_ptr() for t in wx["tail"]],
+                                         pooled.data_ptr() if layers else None, genc.data_ptr(), st), "sdn_wenc_tail_f32")
+    if layers:
+        kept["pooled"] = pooled
+        return genc, kept
+    return genc
+
+
+def style_exact(R, style):
+    """StyleMLP.forward (gancraft_base.py:113-126) on the fixed-order kernel: style [n,128] (or [128]) -> z [n,256].  f64
+    accumulation in k order, one rounding per output: row i is a function of the weights and style row i only."""
+    lib = _lib()
+    w = R.w
+    s = torch.as_tensor(style).to(device=R.dev, dtype=torch.float32)
+    s = s.reshape(-1, s.shape[-1]).contiguous() if s.dim() else s
+    if not (s.dim() == 2 and s.shape[1] == 128 and s.shape[0] >= 1 and R.dev.type == "cuda"):
+        raise ValueError(f"style_exact: needs style [n,128] on a CUDA device, n >= 1 (got {tuple(s.shape)})")
+    names = [f"style_net.fc_layers.{i}" for i in range(5)] + ["style_net.fc_out"]
+    ws = [w[n + ".weight"].detach().to(torch.float32).contiguous() for n in names]
+    bs = [w[n + ".bias"].detach().to(torch.float32).contiguous() for n in names]
+    if [tuple(t.shape) for t in ws] != [(256, 128)] + [(256, 256)] * 5 or any(tuple(b.shape) != (256,) for b in bs):
+        raise ValueError("style_exact: needs the reference's StyleMLP sizes (128 -> 256 x 5 -> 256)")
+    wp = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in ws])
+    bp = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in bs])
+    z = torch.empty((s.shape[0], 256), dtype=torch.float32, device=R.dev)
+    with torch.cuda.device(R.dev):
+        capi.check(lib.sdn_style_mlp_f32(s.data_ptr(), wp, bp, z.data_ptr(), s.shape[0], _stream(R.dev)), "sdn_style_mlp_f32")
+    return z

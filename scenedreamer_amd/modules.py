@@ -17,6 +17,11 @@ SceneDreamer configuration.  Any other call (training with autograd, CPU tensors
 own classes it is the reference's own forward).  There is no silent CPU substitute for the kernels: a CUDA call with
 libsdnative missing raises (capi.lib()).
 
+`ConditionalHashGrid` (layers.py:25-55) and `StyleMLP` (gancraft_base.py:91-126), the two networks upstream of every frame, are here
+too, with a native forward that is OPT-IN per module (`sdn_exact = True`, or SDN_WORLD_EXACT=1 / SDN_STYLE_EXACT=1): the fixed-order
+kernels of csrc/world_f32.hip (fused.world_exact / fused.style_exact).  Without the flag their forward is the composite one, and
+`make_fast` patches the reference's two classes only when it is called on them: dropin.py never does.
+
 Two ways in:
   * `make_fast(RefClass)`: the REFERENCE's own class (its constructor, its parameters, its forward kept as the composite
     path) gets the native forward.  dropin.install_import_hook() does this while the unmodified `imaginaire` package is
@@ -73,6 +78,7 @@ class Backend(P.PrecisionState):
             self._bound.clear()
             self._fused_scene = self._fused_style = self._fused_style_f32 = self._fused_sky = self._fused_sky_f32 = None
             self._mfma_cnns = None
+            self._fused_world_f32 = None
         self.dev = dev
         self._bound[prefix] = (module, key)
         self._zkey.pop(prefix, None)
@@ -84,6 +90,8 @@ class Backend(P.PrecisionState):
             self._fused_scene = None
         if prefix == "sky_net.":
             self._reset_sky_gate()
+        if prefix == "world_encoder.":
+            self._fused_world_f32 = None    # packed convolution weights
         return True
 
     def _reset_sky_gate(self):
@@ -329,11 +337,89 @@ class RenderCNNNative:
         return raw
 
 
+class ConditionalHashGridNative:
+    """forward(height_map [1,1,H,W], semantic_map [1,11,H,W]) -> global_enc [1,2].  The default forward is the composite one (the
+    reference's F.conv2d sequence).  Opt-in `module.sdn_exact = True` (or SDN_WORLD_EXACT=1): the call runs on the fixed-order fp32
+    kernels (csrc/world_f32.hip, fused.world_exact) -- no library solver choice between the maps and the result."""
+    _sdn_native = True
+
+    def native_reason(self, height_map, semantic_map):
+        if not _cuda_f32(height_map, semantic_map):
+            return "needs CUDA float32 tensors"
+        if _wants_grad(self, height_map, semantic_map):
+            return "autograd requested (the kernels are forward-only)"
+        blocks = list(self.conv_blocks)
+        shapes = [tuple(self.hconv_head.weight.shape), tuple(self.sconv_head.weight.shape)]
+        if shapes != [(8, 1, 3, 3), (8, 11, 3, 3)] or len(blocks) != 5 or tuple(self.fc1.weight.shape) != (16, 512) or \
+                tuple(self.fc2.weight.shape) != (2, 16):
+            return "needs the reference's channel counts (num_conv_blocks = 6)"
+        for i, b in enumerate(blocks):
+            c = 16 << i
+            if tuple(b.layers[0].weight.shape) != (c, c, 3, 3) or tuple(b.layers[2].weight.shape) != (2 * c, c, 3, 3):
+                return "needs the reference's channel counts (num_conv_blocks = 6)"
+        if not isinstance(self.act, nn.LeakyReLU) or self.act.negative_slope != 0.2:
+            return "needs LeakyReLU(0.2)"
+        if height_map.dim() != 4 or semantic_map.dim() != 4 or tuple(height_map.shape[:2]) != (1, 1) or \
+                tuple(semantic_map.shape[:2]) != (1, 11) or height_map.shape[2:] != semantic_map.shape[2:] or height_map.numel() == 0:
+            return "needs batch 1 maps [1,1,H,W] and [1,11,H,W]"
+        return None
+
+    def forward(self, height_map, semantic_map):
+        if not bool(self.__dict__.get("sdn_exact", os.environ.get("SDN_WORLD_EXACT", "0") not in ("0", "", "false"))):
+            return self._forward_composite(height_map, semantic_map)
+        why = self.native_reason(height_map, semantic_map)
+        if why is not None:
+            self.__dict__["_sdn_composite_reason"] = why
+            return self._forward_composite(height_map, semantic_map)
+        from . import fused
+        B = _backend(self)
+        B.bind("world_encoder.", self)
+        with torch.no_grad():
+            return fused.world_exact(B, height_map, semantic_map)
+
+
+class StyleMLPNative:
+    """forward(z [N,128]) -> [N,256].  The default forward is the composite one (the reference's F.linear sequence).  Opt-in
+    `module.sdn_exact = True` (or SDN_STYLE_EXACT=1): the call runs on the fixed-order kernel (csrc/world_f32.hip,
+    fused.style_exact) -- f64 accumulation in k order, one rounding per output."""
+    _sdn_native = True
+
+    def native_reason(self, z):
+        if not _cuda_f32(z):
+            return "needs CUDA float32 tensors"
+        if _wants_grad(self, z):
+            return "autograd requested (the kernels are forward-only)"
+        layers = list(self.fc_layers)
+        if len(layers) != 5 or [tuple(f.weight.shape) for f in layers] != [(256, 128)] + [(256, 256)] * 4 or \
+                tuple(self.fc_out.weight.shape) != (256, 256) or any(f.bias is None for f in layers + [self.fc_out]):
+            return "needs style_dim = 128, hidden_channels = 256, out_dim = 256, num_layers = 5"
+        if not (self.normalize_input and self.output_act and isinstance(self.act, nn.LeakyReLU) and self.act.negative_slope == 0.2):
+            return "needs normalize_input, output_act and LeakyReLU(0.2)"
+        if z.dim() != 2 or z.shape[1] != 128 or z.shape[0] < 1:
+            return "z must be [N, 128], N >= 1"
+        return None
+
+    def forward(self, z):
+        if not bool(self.__dict__.get("sdn_exact", os.environ.get("SDN_STYLE_EXACT", "0") not in ("0", "", "false"))):
+            return self._forward_composite(z)
+        why = self.native_reason(z)
+        if why is not None:
+            self.__dict__["_sdn_composite_reason"] = why
+            return self._forward_composite(z)
+        from . import fused
+        B = _backend(self)
+        B.bind("style_net.", self)
+        with torch.no_grad():
+            return fused.style_exact(B, z)
+
+
 def make_fast(ref_cls):
     """Give the reference's LightningMLP / SKYMLP / RenderCNN class the native forward (its own forward stays reachable as
-    `_forward_composite`).  The class object itself is patched, not subclassed: the reference's constructors call
+    `_forward_composite`).  ConditionalHashGrid and StyleMLP are accepted too when a caller names them explicitly (their native
+    forward is opt-in per module, `sdn_exact`); nothing in dropin.py does, so the drop-in's default surface is the three above.  The class object itself is patched, not subclassed: the reference's constructors call
     `super(SKYMLP, self).__init__()` through the module-global name, which must keep meaning the class they are defined in."""
-    mixin = {"LightningMLP": LightningMLPNative, "SKYMLP": SKYMLPNative, "RenderCNN": RenderCNNNative}[ref_cls.__name__]
+    mixin = {"LightningMLP": LightningMLPNative, "SKYMLP": SKYMLPNative, "RenderCNN": RenderCNNNative,
+             "ConditionalHashGrid": ConditionalHashGridNative, "StyleMLP": StyleMLPNative}[ref_cls.__name__]
     if not is_native(ref_cls):
         ref_cls._forward_composite = ref_cls.forward
         ref_cls.forward = mixin.forward
@@ -502,3 +588,57 @@ class RenderCNN(RenderCNNNative, nn.Module):
         y = self.act(film(y + self.conv3b(self.act(self.conv3a(y))), a[2], a[3]))
         y = self.act(y + self.conv4b(self.act(self.conv4a(y))))
         return self.conv4(y)
+
+
+class SRTConvBlock(nn.Module):
+    """layers.py:6-23: conv 3x3 - ReLU - conv 3x3 stride 2 - ReLU, no biases."""
+
+    def __init__(self, idim, hdim=None, odim=None):
+        super().__init__()
+        hdim = idim if hdim is None else hdim
+        odim = 2 * hdim if odim is None else odim
+        self.layers = nn.Sequential(nn.Conv2d(idim, hdim, 3, stride=1, padding=1, bias=False), nn.ReLU(),
+                                    nn.Conv2d(hdim, odim, 3, stride=2, padding=1, bias=False), nn.ReLU())
+
+    def forward(self, x):
+        return self.layers(x)
+
+
+class ConditionalHashGrid(ConditionalHashGridNative, nn.Module):
+    """layers.py:25-55 -- same constructor, parameter names and forward."""
+
+    def __init__(self, num_conv_blocks=6):
+        super().__init__()
+        self.sconv_head = nn.Conv2d(11, 8, kernel_size=3, stride=2, padding=1)
+        self.hconv_head = nn.Conv2d(1, 8, kernel_size=3, stride=2, padding=1)
+        self.conv_blocks = nn.Sequential(*[SRTConvBlock(16 << i) for i in range(num_conv_blocks - 1)])
+        self.fc1 = nn.Linear(16 << (num_conv_blocks - 1), 16)
+        self.fc2 = nn.Linear(16, 2)
+        self.act = nn.LeakyReLU(0.2)
+
+    def _forward_composite(self, height_map, semantic_map):
+        x = torch.cat([self.act(self.hconv_head(height_map)), self.act(self.sconv_head(semantic_map))], dim=1)
+        for block in self.conv_blocks:
+            x = self.act(block(x))
+        x = x.permute(0, 2, 3, 1)
+        x = torch.mean(x.reshape(x.shape[0], -1, x.shape[-1]), dim=1)
+        return torch.tanh(self.fc2(self.act(self.fc1(x))))
+
+
+class StyleMLP(StyleMLPNative, nn.Module):
+    """gancraft_base.py:91-126 -- same constructor, parameter names and forward."""
+
+    def __init__(self, style_dim, out_dim, hidden_channels=256, leaky_relu=True, num_layers=5, normalize_input=True, output_act=True):
+        super().__init__()
+        self.normalize_input, self.output_act = normalize_input, output_act
+        self.fc_layers = nn.ModuleList([nn.Linear(style_dim if i == 0 else hidden_channels, hidden_channels) for i in range(num_layers)])
+        self.fc_out = nn.Linear(hidden_channels, out_dim)
+        self.act = nn.LeakyReLU(negative_slope=0.2) if leaky_relu else nn.ReLU()
+
+    def _forward_composite(self, z):
+        if self.normalize_input:
+            z = F.normalize(z, p=2, dim=-1)
+        for layer in self.fc_layers:
+            z = self.act(layer(z))
+        z = self.fc_out(z)
+        return self.act(z) if self.output_act else z

@@ -11,6 +11,8 @@ from .cnn import F32CNN, MfmaCNN, form_key
 
 EXACT_CNN_MODES = ("torch", "f32")
 EXACT_SKY_MODES = ("torch", "f32")
+EXACT_WORLD_MODES = ("torch", "f32")
+EXACT_STYLE_MODES = ("torch", "f32")
 CNN_MODES = ("mfma", "torch", "f32")
 
 CNN_AUTO_BOUND = 5e-4   # mfma_cnn: largest image difference (max abs) at which the 1-term 3x3 convolutions are accepted
@@ -101,6 +103,15 @@ class PrecisionState:
     # variable SDN_EXACT_SKY, else "torch".  "fused" keeps sky_fused, "unfused" stays on PyTorch.  Every rank of a distributed job
     # must be given the same value: the two differ by fp32 rounding.
     exact_sky = None
+    # The two networks upstream of every frame: the world encoder of set_scene (global_enc) and the style MLP of set_style (z).
+    # "torch" = the reference's F.conv2d / F.linear sequence on the libraries (default); "f32" = fused.world_exact / fused.style_exact,
+    # the fixed-order kernels of csrc/world_f32.hip.  None = the environment variable SDN_EXACT_WORLD / SDN_EXACT_STYLE, else "torch".
+    # Unlike exact_cnn and exact_sky these two apply in set_scene and set_style WHATEVER mode later renders: the encoders run before
+    # a mode exists.  Setting the attribute takes effect at the next set_scene / set_style (Renderer takes both as constructor
+    # keywords, because its __init__ already calls set_scene).  Every rank of a distributed job must be given the same value.
+    exact_world = None
+    exact_style = None
+    encoders = None             # what ran: {"world": "torch" | "f32", "style": "torch" | "f32" | None} (set_scene, set_style)
     # ---- the per-style decisions (calibration.py; forgotten by reset_gates)
     field_gate = None           # the record of calibrate_style: path, measured errors, colour and sky forms
     cnn_calibration = None      # the record of the render CNN's 3x3 rung (calibrate_style, or the windowed gate of mfma_cnn)
@@ -110,6 +121,7 @@ class PrecisionState:
     _mfma_cnns = None           # form key -> cnn.MfmaCNN, "f32" -> cnn.F32CNN
     _fused_scene = _fused_style = _fused_style_f32 = _fused_sky = _fused_sky_f32 = None      # fused.prepare_*
     _fused_lin = _fused_buf = None
+    _fused_world_f32 = None     # fused.prepare_world_exact: the world encoder's packed convolution weights
     _row_cost_cache = None
     _side_stream = _cnn_stream = None
 
@@ -177,6 +189,26 @@ class PrecisionState:
         if v not in EXACT_SKY_MODES:
             raise ValueError(f"Renderer.exact_sky (or SDN_EXACT_SKY) must be 'torch' or 'f32', not {v!r}")
         return v
+
+    def _exact_world_mode(self):
+        """The world encoder set_scene runs: "torch" or "f32" -- in every render mode (it runs before a mode exists)."""
+        v = self.exact_world if self.exact_world is not None else os.environ.get("SDN_EXACT_WORLD", "torch")
+        if v not in EXACT_WORLD_MODES:
+            raise ValueError(f"Renderer.exact_world (or SDN_EXACT_WORLD) must be 'torch' or 'f32', not {v!r}")
+        return v
+
+    def _exact_style_mode(self):
+        """The style MLP set_style runs: "torch" or "f32" -- in every render mode (it runs before a mode exists)."""
+        v = self.exact_style if self.exact_style is not None else os.environ.get("SDN_EXACT_STYLE", "torch")
+        if v not in EXACT_STYLE_MODES:
+            raise ValueError(f"Renderer.exact_style (or SDN_EXACT_STYLE) must be 'torch' or 'f32', not {v!r}")
+        return v
+
+    def _ran(self, which, how):
+        """Record in `encoders` which implementation of the world encoder / style MLP produced the current global_enc / z."""
+        e = dict(self.encoders or {"world": None, "style": None})
+        e[which] = how
+        self.encoders = e
 
     def _resolve_cnn_mode(self, path, cnn_mode):
         """Which render CNN runs on `path` (the path actually taken: "fused", "exact" or "unfused")."""

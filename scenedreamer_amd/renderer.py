@@ -110,7 +110,12 @@ class Renderer(PrecisionState):
     """(The precision knobs, the per-style decisions, their resolvers and the render CNN's forms: precision.PrecisionState.)"""
 
     def __init__(self, weights, scene, device="cuda", num_blocks_early_stop=6, sample_depth=3.0, dists_scale=0.25,
-                 pad=30):
+                 pad=30, exact_world=None, exact_style=None):
+        # (the two encoder knobs of precision.PrecisionState, as keywords: set_scene below already runs the world encoder)
+        if exact_world is not None:
+            self.exact_world = exact_world
+        if exact_style is not None:
+            self.exact_style = exact_style
         self.dev = torch.device(device)
         if self.dev.type == "cuda" and self.dev.index is None:      # "cuda" -> "cuda:<current>": tensor.device carries the index
             self.dev = torch.device("cuda", torch.cuda.current_device())
@@ -148,11 +153,23 @@ class Renderer(PrecisionState):
         self.voxel_dims = tuple(int(v) for v in self.volume.shape)
         if self.volume.is_cuda:
             ops.voxel_occupancy(self.volume)   # built here, on the caller's stream, before any side-stream ray casting
+        world = self._exact_world_mode()
+        with torch.no_grad():
+            if world == "f32":      # the fixed-order kernels (csrc/world_f32.hip): no library between the maps and global_enc
+                self.global_enc = fused.world_exact(self, scene.current_height_map, scene.current_semantic_map)
+            else:
+                self.global_enc = self._world_encoder_torch(scene)
+        self._ran("world", world)
+        self._fused_scene = None
+        self.reset_gates()               # (the collapsed table changes with global_enc; the CNN's record and forms stay)
+
+    def _world_encoder_torch(self, scene):
+        """ConditionalHashGrid.forward (layers.py:40-55) as the reference's op sequence on the libraries."""
         w = self.w
         # (deterministic convolution algorithms: global_enc feeds every sample of every frame, and every rank of a sharded
         # trajectory computes it for itself -- MIOpen's default solver choice is not reproducible from call to call)
         with torch.no_grad(), warnings.catch_warnings(), \
-                torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):  # ConditionalHashGrid.forward, layers.py:40-55
+                torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):
             warnings.simplefilter("ignore")
             h = _lrelu(F.conv2d(scene.current_height_map.to(self.dev), w["world_encoder.hconv_head.weight"],
                                 w["world_encoder.hconv_head.bias"], stride=2, padding=1))
@@ -166,17 +183,23 @@ class Renderer(PrecisionState):
             x = x.permute(0, 2, 3, 1)
             x = x.reshape(x.shape[0], -1, x.shape[-1]).mean(dim=1)
             x = _lrelu(F.linear(x, w["world_encoder.fc1.weight"], w["world_encoder.fc1.bias"]))
-            self.global_enc = torch.tanh(F.linear(x, w["world_encoder.fc2.weight"], w["world_encoder.fc2.bias"]))
-        self._fused_scene = None
-        self.reset_gates()               # (the collapsed table changes with global_enc; the CNN's record and forms stay)
+            return torch.tanh(F.linear(x, w["world_encoder.fc2.weight"], w["world_encoder.fc2.bias"]))
 
-    def set_style(self, style):
+    def _style_mlp_torch(self, style):
+        """StyleMLP.forward (gancraft_base.py:113-126) as the reference's op sequence on the libraries."""
         w = self.w
         with torch.no_grad():
             z = F.normalize(torch.as_tensor(style, dtype=torch.float32, device=self.dev), p=2, dim=-1)
-            for i in range(5):  # StyleMLP.forward, gancraft_base.py:113-126
+            for i in range(5):
                 z = _lrelu(F.linear(z, w[f"style_net.fc_layers.{i}.weight"], w[f"style_net.fc_layers.{i}.bias"]))
-            z = _lrelu(F.linear(z, w["style_net.fc_out.weight"], w["style_net.fc_out.bias"]))
+            return _lrelu(F.linear(z, w["style_net.fc_out.weight"], w["style_net.fc_out.bias"]))
+
+    def set_style(self, style):
+        how = self._exact_style_mode()
+        with torch.no_grad():
+            # "f32": the fixed-order kernel (csrc/world_f32.hip) -- f64 accumulation in k order, no library
+            z = fused.style_exact(self, style) if how == "f32" else self._style_mlp_torch(style)
+        self._ran("style", how)
         self.set_style_code(z)
 
     def set_style_code(self, z):

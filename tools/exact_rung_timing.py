@@ -4,7 +4,7 @@ scene 2048, pose 0 of pattern 0, synthetic weights, style 8888), and writes prof
 
     python tools/exact_rung_timing.py [--reps 10] [--warmup 3] [--out profiles/exact_rung_timing.json] [--only cnn]
 
-Four comparisons, each inside ONE process on one device (devices differ by up to 20 %):
+Six comparisons, each inside ONE process on one device (devices differ by up to 20 %):
   field   fused.field_exact  vs  Renderer.field_unfused over the rays of the same (minimal-apron) window
   frame   render_frame(mode="exact")  vs  render_frame(mode="unfused")
   cnn     cnn.F32CNN (csrc/cnn_f32.hip)  vs  Renderer.render_cnn (PyTorch) on the same 548 x 968 net_out, and
@@ -14,6 +14,10 @@ Four comparisons, each inside ONE process on one device (devices differ by up to
           (the minimal-apron frame's ray count; sky_c and the frame mean on both sides), and the kernel's time against its
           matrix-issue floor: 128-ray groups x 4 waves x chunks issued (fc1's padding included) x 128 MFMAs x 64 cycles / 1 024
           SIMDs / the clock
+  world   fused.world_exact (csrc/world_f32.hip)  vs  Renderer._world_encoder_torch (the F.conv2d sequence of set_scene, with the
+          deterministic-algorithm flags it sets) on the 2048 x 2048 benchmark scene's maps, resident on the device on both sides
+  style   fused.style_exact  vs  Renderer._style_mlp_torch (the F.linear sequence of set_style) on style 8888
+          (both run once per scene / per style, not per frame: no time here is a gate, the two kernels stand on their fixed order)
 --only STEP runs one comparison and replaces only its key in an existing record.
 Every figure is the median of `reps` HIP-event timings after `warmup` runs, the two sides interleaved; `faster` is true when the
 gain exceeds the spread (max - min) of either side.  The field kernel's time is also set against its matrix-issue floor: evaluated
@@ -29,7 +33,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HW, NS, SCENE = (540, 960), 24, 2048
 MFMA_PER_TILE_PASS, MFMA_CYCLES, SIMDS, CLOCK_GHZ = 5888, 64, 1024, 2.4     # the clock: the part's maximum, so the fraction is a lower bound
-STEP_TIMEOUT_S = {"field": 420, "frame": 420, "cnn": 420, "sky": 300}
+STEP_TIMEOUT_S = {"field": 420, "frame": 420, "cnn": 420, "sky": 300, "world": 300, "style": 300}
 SKY_CHUNKS, MFMA_PER_CHUNK = 2 + 4 * 8 + 2, 128      # csrc/sky_f32.hip: fc1 padded to K = 64 (2 chunks) | fc2 .. fc5 | fc_out_c
 SKY_FLOP_PER_RAY = 2 * (33 * 256 + 4 * 256 * 256 + 256 * 64)
 CNN_FLOP_PER_PIXEL, F32_FLOP_PER_CLOCK_PER_SIMD = 5015040, 64
@@ -191,16 +195,49 @@ def step_sky(reps, warmup):
                 tflops=n * SKY_FLOP_PER_RAY / n_["median_ms"] / 1e9)
 
 
+def step_world(reps, warmup):
+    torch, R, _ = _setup()
+    import types
+    from scenedreamer_amd import fused
+    with torch.no_grad():
+        hm = R.scene.current_height_map.to(R.dev, torch.float32).contiguous()
+        sm = R.scene.current_semantic_map.to(R.dev, torch.float32).contiguous()
+        on_dev = types.SimpleNamespace(current_height_map=hm, current_semantic_map=sm)
+        new_fn, old_fn = (lambda: fused.world_exact(R, hm, sm)), (lambda: R._world_encoder_torch(on_dev))
+        g_new, g_old = new_fn(), old_fn()
+        diff = float((g_new - g_old).abs().max())
+        same = bool(torch.equal(new_fn(), g_new))
+        new, old = _time_pair(torch, new_fn, old_fn, reps, warmup)
+    n_, o_, cmp_ = _summary(new, old)
+    return dict(maps=list(hm.shape[2:]), global_enc=g_new.reshape(-1).tolist(), max_abs_diff_global_enc=diff, repeats_bit_for_bit=same,
+                world_exact=n_, world_encoder_torch=o_, **cmp_, ratio_kernel_over_torch=n_["median_ms"] / o_["median_ms"])
+
+
+def step_style(reps, warmup):
+    torch, R, _ = _setup()
+    sys.path.insert(0, ROOT)
+    from scenedreamer_amd import fused, synth
+    with torch.no_grad():
+        style = torch.as_tensor(synth.make_style(8888)).to(R.dev)
+        new_fn, old_fn = (lambda: fused.style_exact(R, style)), (lambda: R._style_mlp_torch(style))
+        z_new, z_old = new_fn(), old_fn()
+        diff = float((z_new - z_old).abs().max())
+        new, old = _time_pair(torch, new_fn, old_fn, reps, warmup)
+    n_, o_, cmp_ = _summary(new, old)
+    return dict(styles=1, max_abs_diff_z=diff, max_abs_z=float(z_old.abs().max()), style_exact=n_, style_mlp_torch=o_, **cmp_,
+                ratio_kernel_over_torch=n_["median_ms"] / o_["median_ms"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "exact_rung_timing.json"))
-    ap.add_argument("--step", choices=["field", "frame", "cnn", "sky"], help="(internal) run one comparison in this process and print its JSON")
-    ap.add_argument("--only", choices=["field", "frame", "cnn", "sky"], help="run this comparison only; the other keys of an existing --out file are kept")
+    ap.add_argument("--step", choices=["field", "frame", "cnn", "sky", "world", "style"], help="(internal) run one comparison in this process and print its JSON")
+    ap.add_argument("--only", choices=["field", "frame", "cnn", "sky", "world", "style"], help="run this comparison only; the other keys of an existing --out file are kept")
     args = ap.parse_args()
     if args.step:
-        res = {"field": step_field, "frame": step_frame, "cnn": step_cnn, "sky": step_sky}[args.step](args.reps, args.warmup)
+        res = {"field": step_field, "frame": step_frame, "cnn": step_cnn, "sky": step_sky, "world": step_world, "style": step_style}[args.step](args.reps, args.warmup)
         print("RESULT " + json.dumps(res))
         return 0
     if args.reps < 10 or args.warmup < 3:
@@ -210,7 +247,7 @@ def main():
     if args.only and os.path.exists(args.out):
         with open(args.out) as f:
             rec = {**json.load(f), "config": rec["config"]}
-    for step in ((args.only,) if args.only else ("field", "frame", "cnn", "sky")):
+    for step in ((args.only,) if args.only else ("field", "frame", "cnn", "sky", "world", "style")):
         cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(args.reps),
                "--warmup", str(args.warmup)]
         r = subprocess.run(cmd, capture_output=True, text=True)
