@@ -498,6 +498,27 @@ int sdn_wenc_tail_f32(const float *rows, int P, const float *fc1_w, const float 
  * SDN_ERR_INVALID for null pointers (the twelve layer pointers included) and n < 1. */
 int sdn_style_mlp_f32(const float *style, const float *const *w6_host, const float *const *b6_host, float *z, int n, sdn_stream_t stream);
 
+/* Baseline JPEG scan encoder (csrc/jpeg.hip): the video sample of the MJPEG-MP4 writer made on the device.  The three entries replace
+ * the Pillow encode of scenedreamer_amd/mp4.py (Mp4MjpegWriter.append: Image.save(format="JPEG", quality, subsampling=0)) and, through
+ * it, the reference's per-frame `fout.append_data(rgb)` (imaginaire/generators/scenedreamer.py:560, :631).
+ * Sequential DCT, 8 bit, three components, 4:4:4, the Annex K quantisation tables scaled by `quality` and the Annex K Huffman tables;
+ * the scan is cut into restart intervals of restart_mcus MCUs (zero DC predictors, byte aligned, joined by RST0 .. RST7).  All
+ * arithmetic is integer and specified to the byte (tests/jpeg_ref.py restates it); no byte depends on n_workgroups (<= 0: defaults).
+ * The caller adds the header (SOI .. SOS, with DRI = restart_mcus) and EOI: scenedreamer_amd/jpeg.py.
+ *
+ * sdn_jpeg_scan_bound: bytes the scan can never exceed: 1248 per MCU (a block is <= 1660 bits = 208 B before stuffing, stuffing at
+ *   most doubles it) + 3 per interval; 0 for a frame the encoder does not take (H, W or restart_mcus outside 1 .. 65535, or a bound
+ *   that does not fit the 32-bit byte count: about 220 Mpixel).
+ * sdn_jpeg_workspace_bytes: size of `workspace` (coefficients, prefix sums, the unstuffed bytes); 0 as above.
+ * sdn_jpeg_encode_scan: rgb_hwc dev uint8 [H,W,3] contiguous -> scan dev (>= sdn_jpeg_scan_bound bytes) and its length in
+ *   *scan_bytes_dev (dev), asynchronous on `stream`.  workspace dev, 256-byte aligned, used by one encode at a time.
+ *   SDN_ERR_UNSUPPORTED before any launch for quality outside 1 .. 100, restart_mcus outside 1 .. 65535, H or W above 65535 or
+ *   negative, a frame over the bound above, and a null pointer on a non-empty frame; H == 0 or W == 0 is a no-op. */
+size_t sdn_jpeg_scan_bound(int H, int W, int restart_mcus);
+size_t sdn_jpeg_workspace_bytes(int H, int W, int restart_mcus);
+int sdn_jpeg_encode_scan(const uint8_t *rgb_hwc, int H, int W, int quality, int restart_mcus, void *workspace, uint8_t *scan,
+                         uint32_t *scan_bytes_dev, int n_workgroups, sdn_stream_t stream);
+
 /* test hook: C[32,32] = A[32,16] * B[16,32] through the MFMA operand layouts field.hip relies on */
 int sdn_debug_mfma_probe(const float *A, const float *B, float *C, sdn_stream_t stream);
 

@@ -40,6 +40,7 @@ SOURCES = {
     "cnn_f32.hip": ["-fno-slp-vectorize"],
     "world_f32.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],  # a fixed order: every fused multiply-add is an explicit fmaf
     "scene.hip": [],
+    "jpeg.hip": [],  # integer arithmetic only
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 

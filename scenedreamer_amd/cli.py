@@ -3,6 +3,7 @@
 
     python -m scenedreamer_amd.cli --output_dir out --seed 8888 [--checkpoint scenedreamer_released.pt]
         [--camera_mode 4 --cam_maxstep 40 --resolution_hw 540 960 --num_samples 40 --cam_ang 72 --scene_size 2048]
+        [--video-backend auto|imageio|mjpeg|mjpeg-gpu]     # mjpeg-gpu: the video's JPEG frames are encoded on the GPU
         [--scene world.npz]     # a saved reference world: voxel_t, heightmap, current_height_map, current_semantic_map, trans_mat
     python -m torch.distributed.run --nproc-per-node N ... -m scenedreamer_amd.cli ...     # frames sharded over GPUs
 
@@ -48,6 +49,10 @@ def build_parser():
                     help="sky MLP of the exact path (--mode exact, or a closed gate with Renderer.fallback = 'exact'): torch = the "
                          "reference's F.linear sequence and a library mean (default; SDN_EXACT_SKY when not given); f32 = the fp32 MFMA "
                          "kernel (fixed summation order, any weight range).  Every rank of a job must be given the same value")
+    ap.add_argument("--video-backend", dest="video_backend", default="auto", choices=["auto", "imageio", "mjpeg", "mjpeg-gpu"],
+                    help="writer of rgb_render.mp4 (single rank only): auto = imageio's H.264 where imageio is importable, else mjpeg; "
+                         "mjpeg = Motion-JPEG encoded by Pillow on one host thread; mjpeg-gpu = the same container with every frame "
+                         "encoded on the GPU (quality 92, 4:4:4), so that only the encoded bytes cross PCIe")
     return ap
 
 
@@ -97,7 +102,7 @@ def main():
         sdist.agree_cnn_precision(R, poses[0], tuple(args.resolution_hw), args.num_samples)
     out = os.path.join(args.output_dir, "rgb_render")
     # (a sharded job writes PNGs from every rank; the video needs the frames in one place, so only a single rank writes it)
-    writer = FrameWriter(out, video_path=(out + ".mp4") if world == 1 else None, fps=10)
+    writer = FrameWriter(out, video_path=(out + ".mp4") if world == 1 else None, fps=10, video_backend=args.video_backend)
     if rank == 0:
         write_scene_maps(out, scene)                                  # scenedreamer.py:562-563
         np.save(os.path.join(out, "style.npy"), np.asarray(style))    # scenedreamer.py:564

@@ -6,6 +6,8 @@ the same kind of artefact with nothing but the standard library + Pillow's JPEG 
 per frame, `ftyp` + `mdat` + `moov` (mvhd / trak / mdia / minf / stbl with stsd, stts, stsc, stsz, co64).
 Players built on ffmpeg (VLC, mpv, browsers via ffmpeg.wasm) read it; the frames are intra-coded, so the file is
 also trivially seekable and a frame can be pulled out with `read_frames` below (used by the tests).
+`append` encodes with Pillow on the calling thread; `append_encoded` takes a sample that is already a JPEG file, which is how
+FrameWriter(video_backend="mjpeg-gpu") hands over the frames it encoded on the GPU (scenedreamer_amd/jpeg.py).
 """
 import io
 import struct
@@ -41,15 +43,25 @@ class Mp4MjpegWriter:
         self.mdat_pos = self.f.tell()
         self.f.write(struct.pack(">I4sQ", 1, b"mdat", 0))      # 64-bit size, patched in close()
 
-    def append(self, rgb):
-        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    def _check_size(self, w, h):
         if self.wh is None:
             self.wh = (w, h)
         elif self.wh != (w, h):
             raise ValueError(f"frame size changed: {self.wh} -> {(w, h)}")
+
+    def append(self, rgb):
+        self._check_size(int(rgb.shape[1]), int(rgb.shape[0]))
         buf = io.BytesIO()
         Image.fromarray(rgb, "RGB").save(buf, format="JPEG", quality=self.quality, subsampling=0)
-        data = buf.getvalue()
+        self._write(buf.getvalue())
+
+    def append_encoded(self, data, w, h):
+        """Append one sample that is already a complete JPEG file of a w x h frame (scenedreamer_amd/jpeg.py encodes on the GPU):
+        the bookkeeping of `append` without the Pillow encode."""
+        self._check_size(int(w), int(h))
+        self._write(data)
+
+    def _write(self, data):
         self.offsets.append(self.f.tell())
         self.sizes.append(len(data))
         self.f.write(data)

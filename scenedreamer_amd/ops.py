@@ -310,3 +310,24 @@ def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, 
                                             grad_inputs.data_ptr(), int(gridtype), int(bool(align_corners)),
                                             _stream(inputs))
     capi.check(rc, "sdn_grid_encode_bwd")
+
+
+def jpeg_encode_scan(u8_hwc, quality, restart_mcus, workspace, scan, nbytes, n_workgroups=0):
+    """sdn_jpeg_encode_scan (csrc/jpeg.hip): the baseline-JPEG scan of a uint8 [H,W,3] frame into `scan`, its length into `nbytes`
+    (one 32-bit element), on the current stream.  It stands where mp4.Mp4MjpegWriter.append runs Pillow's encoder (the reference's
+    `fout.append_data`, scenedreamer.py:560, :631).  `workspace` / `scan`: uint8 tensors of at least sdn_jpeg_workspace_bytes /
+    sdn_jpeg_scan_bound bytes; scenedreamer_amd/jpeg.py owns them in JpegEncoder."""
+    for t, n in ((u8_hwc, "u8_hwc"), (workspace, "workspace"), (scan, "scan"), (nbytes, "nbytes")):
+        _check_dev(t, n)
+        _require(t.device == u8_hwc.device, f"{n} must be on the frame's device")
+    _require(u8_hwc.dtype == torch.uint8 and u8_hwc.dim() == 3 and u8_hwc.shape[2] == 3, "u8_hwc must be a uint8 [H,W,3] tensor")
+    _require(workspace.dtype == torch.uint8 and scan.dtype == torch.uint8, "workspace and scan must be uint8 tensors")
+    _require(nbytes.element_size() == 4 and nbytes.numel() >= 1, "nbytes must hold one 32-bit element")
+    H, W = int(u8_hwc.shape[0]), int(u8_hwc.shape[1])
+    lib = capi.lib()
+    _require(workspace.numel() >= lib.sdn_jpeg_workspace_bytes(H, W, int(restart_mcus)) and
+             scan.numel() >= lib.sdn_jpeg_scan_bound(H, W, int(restart_mcus)), "workspace or scan is smaller than the encoder needs")
+    with torch.cuda.device(u8_hwc.device):
+        rc = lib.sdn_jpeg_encode_scan(u8_hwc.data_ptr(), H, W, int(quality), int(restart_mcus), workspace.data_ptr(), scan.data_ptr(),
+                                      nbytes.data_ptr(), int(n_workgroups), _stream(u8_hwc))
+    capi.check(rc, "sdn_jpeg_encode_scan")

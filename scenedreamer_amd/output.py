@@ -8,6 +8,9 @@ PNG files are encoded by a small pool (zlib releases the GIL; one thread tops ou
 video (`video_path`, the reference's `output_dir + '.mp4'` at 10 fps, scenedreamer.py:560, :631) is appended in frame
 order by its own thread: through imageio's writer (H.264 via ffmpeg, what the reference produces) where imageio is
 importable, else through scenedreamer_amd/mp4.py (Motion-JPEG in an MP4 container, no external dependency).
+With `video_backend="mjpeg-gpu"` (opt-in, never chosen by "auto") the JPEG sample is encoded on the GPU from the same uint8 tensor
+the PNG is written from (scenedreamer_amd/jpeg.py, csrc/jpeg.hip): only the encoded bytes cross PCIe for the video, the video thread
+appends bytes instead of running Pillow's encoder, and with `output_dir=None` the raw frame is not copied to the host at all.
 `write_scene_maps` writes the two per-trajectory maps of scenedreamer.py:562-563."""
 import os
 import queue
@@ -67,8 +70,9 @@ class _ImageioVideo:
 
 
 def open_video(path, fps=10, backend="auto"):
-    """backend: "imageio" (H.264 through ffmpeg, the reference's writer), "mjpeg" (scenedreamer_amd/mp4.py), or "auto" =
-    imageio if it is importable, else mjpeg."""
+    """backend: "imageio" (H.264 through ffmpeg, the reference's writer), "mjpeg" (scenedreamer_amd/mp4.py), "mjpeg-gpu" (the same
+    container; the caller passes samples already encoded by scenedreamer_amd/jpeg.py to `append_encoded`), or "auto" = imageio if
+    it is importable, else mjpeg."""
     if backend in ("auto", "imageio"):
         try:
             return _ImageioVideo(path, fps)
@@ -88,7 +92,10 @@ def to_uint8_hwc(img):
 
 class FrameWriter:
     def __init__(self, output_dir, fmt="png", png_compress_level=4, depth=8, video_path=None, fps=10, png_threads=3,
-                 video_backend="auto"):
+                 video_backend="auto", video_quality=92, video_restart_mcus=None, video_slots=2):
+        """video_backend: see open_video.  video_quality / video_restart_mcus / video_slots are read by "mjpeg-gpu" only: JPEG
+        quality, MCUs per restart interval (None: one MCU row) and the number of scan buffers, i.e. of frames that may be encoded
+        but not yet copied to the host (each is sdn_jpeg_scan_bound bytes: 1248 B per 8 x 8 pixels)."""
         self.dir = output_dir
         if output_dir:
             os.makedirs(output_dir, exist_ok=True)
@@ -101,6 +108,11 @@ class FrameWriter:
         self._lock = threading.Lock()
         self.threads = [threading.Thread(target=self._run, daemon=True) for _ in range(max(1, png_threads if output_dir else 1))]
         self.video = None
+        self.gpu_video = bool(video_path) and video_backend == "mjpeg-gpu"
+        self.video_quality, self.video_restart_mcus = int(video_quality), video_restart_mcus
+        self._slots = queue.Queue()                 # free (encoder, pinned byte count) pairs, made at the first submit
+        self._n_slots = max(1, int(video_slots))
+        self._jpeg = None
         if video_path:
             self.video = open_video(video_path, fps, video_backend)
             self.vq = queue.Queue(maxsize=depth)
@@ -113,6 +125,8 @@ class FrameWriter:
         """Enqueue frame `index`; returns immediately (blocks only when `depth` frames are already in flight)."""
         if self.err:
             raise self.err
+        if self.gpu_video:
+            return self._submit_gpu_video(img, index)
         if img.is_cuda:
             u8 = to_uint8_hwc(img)
             host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
@@ -127,6 +141,63 @@ class FrameWriter:
         if self.video is not None:
             self.vq.put((index, host, ready))
         self.q.put((index, host, ready))
+
+    def _submit_gpu_video(self, img, index):
+        """The "mjpeg-gpu" form of submit: the uint8 frame is made once; the side stream encodes it (csrc/jpeg.hip) and copies the
+        4-byte scan length to pinned memory, and, when PNGs are written too, the raw frame as before.  The scan itself is copied by
+        the video thread, which alone waits for the length."""
+        if not img.is_cuda:
+            raise ValueError('video_backend="mjpeg-gpu" encodes on the GPU: the image must be a CUDA tensor')
+        from . import jpeg
+        u8 = to_uint8_hwc(img)
+        H, W = int(u8.shape[0]), int(u8.shape[1])
+        if self._jpeg is None:
+            first = jpeg.JpegEncoder(H, W, self.video_quality, self.video_restart_mcus, device=u8.device)
+            self._jpeg = [first] + [jpeg.JpegEncoder(H, W, self.video_quality, self.video_restart_mcus, device=u8.device,
+                                                     workspace=first.workspace) for _ in range(self._n_slots - 1)]
+            self.vstream = torch.cuda.Stream(u8.device)
+            for enc in self._jpeg:
+                self._slots.put((enc, torch.zeros(1, dtype=torch.int32, pin_memory=True)))
+        if (H, W) != (self._jpeg[0].H, self._jpeg[0].W):
+            raise ValueError(f"frame size changed: {(self._jpeg[0].W, self._jpeg[0].H)} -> {(W, H)}")
+        slot = self._slots.get()                    # blocks while every scan buffer waits for the video thread's copy
+        enc, nbytes_host = slot
+        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True) if self.dir else None
+        ready, len_ready = torch.cuda.Event(), torch.cuda.Event()
+        try:
+            self.stream.wait_stream(torch.cuda.current_stream(u8.device))
+            with torch.cuda.stream(self.stream):
+                _, nbytes = enc.encode(u8)
+                nbytes_host.copy_(nbytes, non_blocking=True)
+                len_ready.record()
+                if host is not None:
+                    host.copy_(u8, non_blocking=True)
+                    ready.record()
+            u8.record_stream(self.stream)
+        except Exception:
+            self._slots.put(slot)
+            raise
+        self.vq.put((index, slot, len_ready))
+        if host is not None:
+            self.q.put((index, host, ready))
+
+    def _fetch_encoded(self, slot, len_ready):
+        """Video thread: wait for the scan length, copy exactly that many scan bytes to pinned memory on the thread's own stream,
+        free the scan buffer for the next encode and return the complete JPEG file."""
+        from . import jpeg
+        enc, nbytes_host = slot
+        try:
+            len_ready.synchronize()
+            n = int(nbytes_host.item()) & 0xFFFFFFFF
+            if n > enc.bound:
+                raise RuntimeError(f"encoded scan of {n} bytes exceeds the bound of {enc.bound}")
+            host = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.device(enc.device), torch.cuda.stream(self.vstream):
+                host.copy_(enc.scan[:n], non_blocking=True)     # ordered behind the encode by len_ready, which has completed
+                self.vstream.synchronize()
+        finally:
+            self._slots.put(slot)
+        return enc.header + host.numpy().tobytes() + jpeg.EOI
 
     def _run(self):
         while True:
@@ -162,24 +233,36 @@ class FrameWriter:
             item = self.vq.get()
             if item is None:
                 for k in sorted(pending):
-                    self.video.append(pending[k])
+                    self._append_video(pending[k])
                 return
             index, host, ready = item
             try:
-                if ready is not None:
-                    ready.synchronize()
+                if self.gpu_video:
+                    pending[index] = self._fetch_encoded(host, ready)
+                else:
+                    if ready is not None:
+                        ready.synchronize()
+                    pending[index] = host.numpy()
                 if nxt is None:
                     nxt = index
-                pending[index] = host.numpy()
                 while pending:
                     if nxt not in pending:
                         if len(pending) <= limit and min(pending) > nxt:
                             break                       # still plausible that `nxt` arrives
                         nxt = min(pending)              # gap (strided / late indices): continue from the smallest one held
-                    self.video.append(pending.pop(nxt))
+                    self._append_video(pending.pop(nxt))
                     nxt += 1
             except Exception as e:
                 self.err = e
+
+    def _append_video(self, frame):
+        if self.gpu_video:
+            self.video.append_encoded(frame, self._jpeg[0].W, self._jpeg[0].H)
+            if not self.dir:                        # video only: no PNG worker sees the frame, so it is counted here
+                with self._lock:
+                    self.frames_done += 1
+        else:
+            self.video.append(frame)
 
     def close(self):
         for _ in self.threads:
