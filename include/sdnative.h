@@ -519,6 +519,31 @@ size_t sdn_jpeg_workspace_bytes(int H, int W, int restart_mcus);
 int sdn_jpeg_encode_scan(const uint8_t *rgb_hwc, int H, int W, int quality, int restart_mcus, void *workspace, uint8_t *scan,
                          uint32_t *scan_bytes_dev, int n_workgroups, sdn_stream_t stream);
 
+/* Lossless PNG encoder (csrc/png.hip): the zlib stream of the IDAT chunk of the per-frame PNG made on the device.  The three entries
+ * replace the Pillow encode of scenedreamer_amd/output.py (FrameWriter: Image.save(compress_level)) and, through it, the reference's
+ * per-frame write_img (imaginaire/generators/scenedreamer.py:512-518, called at :629-631).
+ * 8-bit RGB (colour type 2, no interlace).  filter_mode 0 .. 4 forces one PNG filter type for every row; 5 chooses per row the type
+ * with the smallest sum of (b < 128 ? b : 256 - b) over its filtered bytes (the smallest type on a tie).  Tokens are literals and
+ * matches at distance 1 made per row; one dynamic-Huffman deflate block per frame whose literal/length code is built on the device
+ * from the frame's histogram; zlib wrapper 78 01 .. Adler-32.  All arithmetic is integer and specified to the byte (tests/png_ref.py
+ * restates it); no byte depends on n_workgroups (<= 0: defaults).  The caller adds the signature, IHDR, the IDAT framing with its
+ * CRC-32 and IEND: scenedreamer_amd/png.py.
+ *
+ * sdn_png_stream_bound (scenedreamer.py:512-518): bytes the zlib stream can never exceed: 15 bits per byte of the filtered stream
+ *   (H (1 + 3W) bytes; a match costs <= 21 bits for >= 3 of them) and for the end-of-block code, 2083 bits of block header, rounded up
+ *   to a byte, + 6 (78 01 and the Adler-32), rounded up to a multiple of 4; 0 for a frame the encoder does not take (H or W outside
+ *   1 .. 65535, or a bound whose bit count does not fit 32 bits: about 95 Mpixel).
+ * sdn_png_workspace_bytes (scenedreamer.py:512-518): size of `workspace` (the filtered stream, one uint16 token per byte of it, the
+ *   histogram, the codes, per-256-byte bit counts and Adler pairs); 0 as above.
+ * sdn_png_encode (scenedreamer.py:512-518): rgb_hwc dev uint8 [H,W,3] contiguous -> zstream dev (>= sdn_png_stream_bound bytes, 4-byte
+ *   aligned) and its length in *zbytes_dev (dev), asynchronous on `stream`.  workspace dev, 256-byte aligned, used by one encode at a
+ *   time.  SDN_ERR_UNSUPPORTED before any launch for filter_mode outside 0 .. 5, H or W above 65535 or negative, a frame over the
+ *   bound above ("too large"), and a null pointer on a non-empty frame; H == 0 or W == 0 is a no-op. */
+size_t sdn_png_stream_bound(int H, int W);
+size_t sdn_png_workspace_bytes(int H, int W);
+int sdn_png_encode(const uint8_t *rgb_hwc, int H, int W, int filter_mode, void *workspace, uint8_t *zstream, uint32_t *zbytes_dev,
+                   int n_workgroups, sdn_stream_t stream);
+
 /* test hook: C[32,32] = A[32,16] * B[16,32] through the MFMA operand layouts field.hip relies on */
 int sdn_debug_mfma_probe(const float *A, const float *B, float *C, sdn_stream_t stream);
 

@@ -41,6 +41,7 @@ SOURCES = {
     "world_f32.hip": ["-fno-slp-vectorize", "-ffp-contract=off"],  # a fixed order: every fused multiply-add is an explicit fmaf
     "scene.hip": [],
     "jpeg.hip": [],  # integer arithmetic only
+    "png.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 

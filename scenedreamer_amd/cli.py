@@ -4,6 +4,7 @@
     python -m scenedreamer_amd.cli --output_dir out --seed 8888 [--checkpoint scenedreamer_released.pt]
         [--camera_mode 4 --cam_maxstep 40 --resolution_hw 540 960 --num_samples 40 --cam_ang 72 --scene_size 2048]
         [--video-backend auto|imageio|mjpeg|mjpeg-gpu]     # mjpeg-gpu: the video's JPEG frames are encoded on the GPU
+        [--png-backend pillow|gpu]                         # gpu: the PNG frames are filtered and deflated on the GPU
         [--scene world.npz]     # a saved reference world: voxel_t, heightmap, current_height_map, current_semantic_map, trans_mat
     python -m torch.distributed.run --nproc-per-node N ... -m scenedreamer_amd.cli ...     # frames sharded over GPUs
 
@@ -53,6 +54,10 @@ def build_parser():
                     help="writer of rgb_render.mp4 (single rank only): auto = imageio's H.264 where imageio is importable, else mjpeg; "
                          "mjpeg = Motion-JPEG encoded by Pillow on one host thread; mjpeg-gpu = the same container with every frame "
                          "encoded on the GPU (quality 92, 4:4:4), so that only the encoded bytes cross PCIe")
+    ap.add_argument("--png-backend", dest="png_backend", default="pillow", choices=["pillow", "gpu"],
+                    help="encoder of rgb_render/%%05d.png: pillow = zlib at compress_level 4 on a pool of host threads; gpu = the "
+                         "filters, one dynamic-Huffman deflate block and the Adler-32 on the GPU (lossless, the same pixels; larger "
+                         "files where the image repeats at a distance), so that only the encoded bytes cross PCIe")
     return ap
 
 
@@ -102,7 +107,8 @@ def main():
         sdist.agree_cnn_precision(R, poses[0], tuple(args.resolution_hw), args.num_samples)
     out = os.path.join(args.output_dir, "rgb_render")
     # (a sharded job writes PNGs from every rank; the video needs the frames in one place, so only a single rank writes it)
-    writer = FrameWriter(out, video_path=(out + ".mp4") if world == 1 else None, fps=10, video_backend=args.video_backend)
+    writer = FrameWriter(out, video_path=(out + ".mp4") if world == 1 else None, fps=10, video_backend=args.video_backend,
+                         png_backend=args.png_backend)
     if rank == 0:
         write_scene_maps(out, scene)                                  # scenedreamer.py:562-563
         np.save(os.path.join(out, "style.npy"), np.asarray(style))    # scenedreamer.py:564

@@ -331,3 +331,24 @@ def jpeg_encode_scan(u8_hwc, quality, restart_mcus, workspace, scan, nbytes, n_w
         rc = lib.sdn_jpeg_encode_scan(u8_hwc.data_ptr(), H, W, int(quality), int(restart_mcus), workspace.data_ptr(), scan.data_ptr(),
                                       nbytes.data_ptr(), int(n_workgroups), _stream(u8_hwc))
     capi.check(rc, "sdn_jpeg_encode_scan")
+
+
+def png_encode(u8_hwc, filter_mode, workspace, zstream, nbytes, n_workgroups=0):
+    """sdn_png_encode (csrc/png.hip): the zlib stream of the PNG of a uint8 [H,W,3] frame into `zstream`, its length into `nbytes`
+    (one 32-bit element), on the current stream.  It stands where FrameWriter runs Pillow's encoder (the reference's write_img,
+    scenedreamer.py:512-518).  `workspace` / `zstream`: uint8 tensors of at least sdn_png_workspace_bytes / sdn_png_stream_bound
+    bytes; scenedreamer_amd/png.py owns them in PngEncoder."""
+    for t, n in ((u8_hwc, "u8_hwc"), (workspace, "workspace"), (zstream, "zstream"), (nbytes, "nbytes")):
+        _check_dev(t, n)
+        _require(t.device == u8_hwc.device, f"{n} must be on the frame's device")
+    _require(u8_hwc.dtype == torch.uint8 and u8_hwc.dim() == 3 and u8_hwc.shape[2] == 3, "u8_hwc must be a uint8 [H,W,3] tensor")
+    _require(workspace.dtype == torch.uint8 and zstream.dtype == torch.uint8, "workspace and zstream must be uint8 tensors")
+    _require(nbytes.element_size() == 4 and nbytes.numel() >= 1, "nbytes must hold one 32-bit element")
+    H, W = int(u8_hwc.shape[0]), int(u8_hwc.shape[1])
+    lib = capi.lib()
+    _require(workspace.numel() >= lib.sdn_png_workspace_bytes(H, W) and zstream.numel() >= lib.sdn_png_stream_bound(H, W),
+             "workspace or zstream is smaller than the encoder needs")
+    with torch.cuda.device(u8_hwc.device):
+        rc = lib.sdn_png_encode(u8_hwc.data_ptr(), H, W, int(filter_mode), workspace.data_ptr(), zstream.data_ptr(), nbytes.data_ptr(),
+                                int(n_workgroups), _stream(u8_hwc))
+    capi.check(rc, "sdn_png_encode")

@@ -11,6 +11,9 @@ importable, else through scenedreamer_amd/mp4.py (Motion-JPEG in an MP4 containe
 With `video_backend="mjpeg-gpu"` (opt-in, never chosen by "auto") the JPEG sample is encoded on the GPU from the same uint8 tensor
 the PNG is written from (scenedreamer_amd/jpeg.py, csrc/jpeg.hip): only the encoded bytes cross PCIe for the video, the video thread
 appends bytes instead of running Pillow's encoder, and with `output_dir=None` the raw frame is not copied to the host at all.
+With `png_backend="gpu"` (opt-in; "pillow" is the default and its files are unchanged) the PNG's zlib stream is made on the GPU as well
+(scenedreamer_amd/png.py, csrc/png.hip): the side stream encodes, a PNG worker copies exactly the encoded bytes, adds the chunk
+framing with its CRC-32 and writes the file; together with "mjpeg-gpu" the raw frame never leaves the device.
 `write_scene_maps` writes the two per-trajectory maps of scenedreamer.py:562-563."""
 import os
 import queue
@@ -92,14 +95,23 @@ def to_uint8_hwc(img):
 
 class FrameWriter:
     def __init__(self, output_dir, fmt="png", png_compress_level=4, depth=8, video_path=None, fps=10, png_threads=3,
-                 video_backend="auto", video_quality=92, video_restart_mcus=None, video_slots=2):
+                 video_backend="auto", video_quality=92, video_restart_mcus=None, video_slots=2, png_backend="pillow", png_slots=2,
+                 png_filter="adaptive"):
         """video_backend: see open_video.  video_quality / video_restart_mcus / video_slots are read by "mjpeg-gpu" only: JPEG
         quality, MCUs per restart interval (None: one MCU row) and the number of scan buffers, i.e. of frames that may be encoded
-        but not yet copied to the host (each is sdn_jpeg_scan_bound bytes: 1248 B per 8 x 8 pixels)."""
+        but not yet copied to the host (each is sdn_jpeg_scan_bound bytes: 1248 B per 8 x 8 pixels).
+        png_backend: "pillow" (Image.save with png_compress_level) or "gpu" (scenedreamer_amd/png.py: needs fmt="png" and CUDA images,
+        ignores png_compress_level).  png_slots / png_filter are read by "gpu" only: the number of stream buffers (each is
+        sdn_png_stream_bound bytes: 15 bits per byte of the frame) and the PngEncoder's `filter`."""
+        if png_backend not in ("pillow", "gpu"):
+            raise ValueError(f'png_backend must be "pillow" or "gpu", got {png_backend!r}')
+        if png_backend == "gpu" and fmt != "png":
+            raise ValueError(f'png_backend="gpu" writes PNG files: fmt must be "png", got {fmt!r}')
         self.dir = output_dir
         if output_dir:
             os.makedirs(output_dir, exist_ok=True)
-        self.fmt = fmt if (fmt != "png" or Image is not None) else "npy"
+        self.gpu_png = png_backend == "gpu" and bool(output_dir)
+        self.fmt = fmt if (fmt != "png" or Image is not None or self.gpu_png) else "npy"
         self.level = png_compress_level
         self.q = queue.Queue(maxsize=depth)
         self.stream = torch.cuda.Stream() if torch.cuda.is_available() else None
@@ -113,6 +125,11 @@ class FrameWriter:
         self._slots = queue.Queue()                 # free (encoder, pinned byte count) pairs, made at the first submit
         self._n_slots = max(1, int(video_slots))
         self._jpeg = None
+        self._png_backend, self._png_filter = png_backend, png_filter
+        self._pslots = queue.Queue()                # free (PngEncoder, pinned byte count) pairs, made at the first submit
+        self._n_pslots = max(1, int(png_slots))
+        self._png = None
+        self._tls = threading.local()               # each PNG worker's own copy stream
         if video_path:
             self.video = open_video(video_path, fps, video_backend)
             self.vq = queue.Queue(maxsize=depth)
@@ -125,8 +142,10 @@ class FrameWriter:
         """Enqueue frame `index`; returns immediately (blocks only when `depth` frames are already in flight)."""
         if self.err:
             raise self.err
-        if self.gpu_video:
-            return self._submit_gpu_video(img, index)
+        if self._png_backend == "gpu" and not img.is_cuda:
+            raise ValueError('png_backend="gpu" encodes on the GPU: the image must be a CUDA tensor')
+        if self.gpu_video or self.gpu_png:
+            return self._submit_gpu(img, index)
         if img.is_cuda:
             u8 = to_uint8_hwc(img)
             host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
@@ -142,44 +161,88 @@ class FrameWriter:
             self.vq.put((index, host, ready))
         self.q.put((index, host, ready))
 
-    def _submit_gpu_video(self, img, index):
-        """The "mjpeg-gpu" form of submit: the uint8 frame is made once; the side stream encodes it (csrc/jpeg.hip) and copies the
-        4-byte scan length to pinned memory, and, when PNGs are written too, the raw frame as before.  The scan itself is copied by
-        the video thread, which alone waits for the length."""
+    def _submit_gpu(self, img, index):
+        """The form of submit with a GPU encoder ("mjpeg-gpu", png_backend="gpu" or both): the uint8 frame is made once; the side
+        stream encodes it (csrc/jpeg.hip, csrc/png.hip) and copies each 4-byte length to pinned memory, and the raw frame only for
+        a consumer that still encodes on the CPU (the Pillow PNG pool, or a CPU video backend).  The encoded bytes are copied by the
+        video thread / a PNG worker, which alone wait for their length."""
         if not img.is_cuda:
             raise ValueError('video_backend="mjpeg-gpu" encodes on the GPU: the image must be a CUDA tensor')
-        from . import jpeg
         u8 = to_uint8_hwc(img)
         H, W = int(u8.shape[0]), int(u8.shape[1])
-        if self._jpeg is None:
+        if self.gpu_video and self._jpeg is None:
+            from . import jpeg
             first = jpeg.JpegEncoder(H, W, self.video_quality, self.video_restart_mcus, device=u8.device)
             self._jpeg = [first] + [jpeg.JpegEncoder(H, W, self.video_quality, self.video_restart_mcus, device=u8.device,
                                                      workspace=first.workspace) for _ in range(self._n_slots - 1)]
             self.vstream = torch.cuda.Stream(u8.device)
             for enc in self._jpeg:
                 self._slots.put((enc, torch.zeros(1, dtype=torch.int32, pin_memory=True)))
-        if (H, W) != (self._jpeg[0].H, self._jpeg[0].W):
-            raise ValueError(f"frame size changed: {(self._jpeg[0].W, self._jpeg[0].H)} -> {(W, H)}")
-        slot = self._slots.get()                    # blocks while every scan buffer waits for the video thread's copy
-        enc, nbytes_host = slot
-        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True) if self.dir else None
-        ready, len_ready = torch.cuda.Event(), torch.cuda.Event()
+        if self.gpu_png and self._png is None:
+            from . import png
+            first = png.PngEncoder(H, W, self._png_filter, device=u8.device)
+            self._png = [first] + [png.PngEncoder(H, W, self._png_filter, device=u8.device, workspace=first.workspace)
+                                   for _ in range(self._n_pslots - 1)]
+            for enc in self._png:
+                self._pslots.put((enc, torch.zeros(1, dtype=torch.int32, pin_memory=True)))
+        for encs in (self._jpeg, self._png):
+            if encs is not None and (H, W) != (encs[0].H, encs[0].W):
+                raise ValueError(f"frame size changed: {(encs[0].W, encs[0].H)} -> {(W, H)}")
+        # blocks while every buffer of a kind waits for its consumer's copy
+        vslot = self._slots.get() if self.gpu_video else None
+        pslot = self._pslots.get() if self.gpu_png else None
+        raw_for_png = bool(self.dir) and not self.gpu_png
+        raw_for_video = self.video is not None and not self.gpu_video
+        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True) if (raw_for_png or raw_for_video) else None
+        ready, vlen_ready, plen_ready = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
         try:
             self.stream.wait_stream(torch.cuda.current_stream(u8.device))
             with torch.cuda.stream(self.stream):
-                _, nbytes = enc.encode(u8)
-                nbytes_host.copy_(nbytes, non_blocking=True)
-                len_ready.record()
+                if vslot is not None:
+                    _, nbytes = vslot[0].encode(u8)
+                    vslot[1].copy_(nbytes, non_blocking=True)
+                    vlen_ready.record()
+                if pslot is not None:
+                    _, nbytes = pslot[0].encode(u8)
+                    pslot[1].copy_(nbytes, non_blocking=True)
+                    plen_ready.record()
                 if host is not None:
                     host.copy_(u8, non_blocking=True)
                     ready.record()
             u8.record_stream(self.stream)
         except Exception:
-            self._slots.put(slot)
+            if vslot is not None:
+                self._slots.put(vslot)
+            if pslot is not None:
+                self._pslots.put(pslot)
             raise
-        self.vq.put((index, slot, len_ready))
-        if host is not None:
+        if self.video is not None:
+            self.vq.put((index, vslot, vlen_ready) if self.gpu_video else (index, host, ready))
+        if self.gpu_png:
+            self.q.put((index, pslot, plen_ready))
+        elif self.dir:
             self.q.put((index, host, ready))
+
+    def _fetch_png(self, slot, len_ready):
+        """PNG worker: wait for the stream length, copy exactly that many bytes to pinned memory on the worker's own stream, free the
+        stream buffer for the next encode and return the complete file (the IDAT CRC-32 is computed here, on the host)."""
+        from . import png
+        enc, nbytes_host = slot
+        try:
+            len_ready.synchronize()
+            n = int(nbytes_host.item()) & 0xFFFFFFFF
+            if n > enc.bound:
+                raise RuntimeError(f"encoded stream of {n} bytes exceeds the bound of {enc.bound}")
+            host = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.device(enc.device):
+                if getattr(self._tls, "stream", None) is None:
+                    self._tls.stream = torch.cuda.Stream(enc.device)
+                with torch.cuda.stream(self._tls.stream):
+                    host.copy_(enc.zstream[:n], non_blocking=True)  # ordered behind the encode by len_ready, which has completed
+                    self._tls.stream.synchronize()
+        finally:
+            self._pslots.put(slot)
+        return png.file(enc.H, enc.W, host.numpy().tobytes())
 
     def _fetch_encoded(self, slot, len_ready):
         """Video thread: wait for the scan length, copy exactly that many scan bytes to pinned memory on the thread's own stream,
@@ -206,6 +269,13 @@ class FrameWriter:
                 return
             index, host, ready = item
             try:
+                if self.gpu_png:
+                    data = self._fetch_png(host, ready)
+                    with open(os.path.join(self.dir, f"{index:05d}.png"), "wb") as f:
+                        f.write(data)
+                    with self._lock:
+                        self.frames_done += 1
+                    continue
                 if ready is not None:
                     ready.synchronize()
                 arr = host.numpy()
