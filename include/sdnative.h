@@ -544,6 +544,36 @@ size_t sdn_png_workspace_bytes(int H, int W);
 int sdn_png_encode(const uint8_t *rgb_hwc, int H, int W, int filter_mode, void *workspace, uint8_t *zstream, uint32_t *zbytes_dev,
                    int n_workgroups, sdn_stream_t stream);
 
+/* Depth and opacity maps of a frame (csrc/maps.hip): the tail of Generator.inference_givenstyle_depth (imaginaire/generators/
+ * scenedreamer.py:636-851) on the per-sample arrays `weights` and `depth` of sdn_field_aux.  Both entries only enqueue on `stream`; no
+ * bit of any output depends on n_workgroups (<= 0: one per CU).  All arithmetic is specified to the bit (tests/depth_maps_ref.py
+ * restates it).
+ *
+ * sdn_depth_maps replaces `depth_map = torch.sum(weights * rand_depth, -2)` (scenedreamer.py:816), the crop of :821-823 and the
+ *   `tmp.min()` / `tmp.max()` over `fake_depth > 0` of :835-838.
+ *   weights, sample_depth  dev f32 [rows*cols, num_samples], the window's row-major ray order (what the aux protocol delivers)
+ *   depth_map              dev f32 [(rows-2*crop) * (cols-2*crop)]: per kept ray the products w[s] * z[s] accumulated in f64 for s
+ *                          ascending from zero, rounded to f32 once
+ *   opacity                NULL, or dev f32 of the same size: the same accumulation over w[s] alone
+ *   range_bits             dev u32[2]: the f32 bit patterns of the smallest and the largest depth_map value that is > 0 and finite,
+ *                          by integer atomicMin / atomicMax (no float atomics).  The entry initialises the pair itself on `stream` to
+ *                          {0x7F800000, 0}: a reused buffer needs nothing from the caller, range_bits[1] == 0 means that no pixel
+ *                          hit anything.
+ * sdn_depth_quantise replaces `(tmp - tmp.min()) / (tmp.max() - tmp.min())`, `fake_depth[~mmask] = 1` (scenedreamer.py:838-841) and
+ *   the conversion of `* 255` by cv2.imwrite (:844).
+ *   depth_map dev f32 [n]; range_bits dev u32[2] = bit patterns of (lo, hi); bits 8 or 16; out dev uint8 / uint16 [n].
+ *   d > 0 and finite: t = (d - lo) / (hi - lo) in f32 with a correctly rounded division, 0 when hi == lo, clamped to [0, 1];
+ *   v = rintf(t * (2^bits - 1)), ties to even -- OpenCV's documented float -> 8-bit conversion (saturate_cast of convertTo), taken
+ *   from its documentation, not measured against an OpenCV build.  Every other d, NaN included: 2^bits - 1.
+ *   With the pair sdn_depth_maps wrote and bits = 8 this is the reference's depth/%05d.png; with a pair the caller fills (lo = 0,
+ *   hi = depth_max) and bits = 16 it is a metric depth comparable across frames, which the per-frame normalisation is not.
+ * SDN_ERR_INVALID before any launch for null pointers (opacity excepted), rows / cols / num_samples / n < 1, crop < 0, 2*crop >= rows
+ * or cols, bits other than 8 and 16, rows*cols*num_samples or n beyond int32. */
+int sdn_depth_maps(const float *weights, const float *sample_depth, int rows, int cols, int num_samples, int crop, float *depth_map,
+                   float *opacity, uint32_t *range_bits, int n_workgroups, sdn_stream_t stream);
+int sdn_depth_quantise(const float *depth_map, int64_t n, const uint32_t *range_bits, int bits, void *out, int n_workgroups,
+                       sdn_stream_t stream);
+
 /* test hook: C[32,32] = A[32,16] * B[16,32] through the MFMA operand layouts field.hip relies on */
 int sdn_debug_mfma_probe(const float *A, const float *B, float *C, sdn_stream_t stream);
 

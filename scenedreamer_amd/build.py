@@ -42,6 +42,7 @@ SOURCES = {
     "scene.hip": [],
     "jpeg.hip": [],  # integer arithmetic only
     "png.hip": [],
+    "maps.hip": ["-ffp-contract=off"],  # bit-exact vs tests/depth_maps_ref.py: subtract, divide, multiply each rounded on its own
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 

@@ -111,6 +111,8 @@ _SIGNATURES = {
     "sdn_png_stream_bound": (ctypes.c_size_t, [c_i, c_i]),
     "sdn_png_workspace_bytes": (ctypes.c_size_t, [c_i, c_i]),
     "sdn_png_encode": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p]),
+    "sdn_depth_maps": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p]),
+    "sdn_depth_quantise": (c_i, [c_p, c_i64, c_p, c_i, c_p, c_i, c_p]),
     "sdn_debug_mfma_probe": (c_i, [c_p, c_p, c_p, c_p]),
 }
 # entry points added by later kernels register themselves here (name -> (restype, argtypes))

@@ -5,6 +5,7 @@
         [--camera_mode 4 --cam_maxstep 40 --resolution_hw 540 960 --num_samples 40 --cam_ang 72 --scene_size 2048]
         [--video-backend auto|imageio|mjpeg|mjpeg-gpu]     # mjpeg-gpu: the video's JPEG frames are encoded on the GPU
         [--png-backend pillow|gpu]                         # gpu: the PNG frames are filtered and deflated on the GPU
+        [--depth-maps off|u8|u16 [--depth-max D]]          # also <output_dir>/depth/%05d.png (inference_givenstyle_depth)
         [--scene world.npz]     # a saved reference world: voxel_t, heightmap, current_height_map, current_semantic_map, trans_mat
     python -m torch.distributed.run --nproc-per-node N ... -m scenedreamer_amd.cli ...     # frames sharded over GPUs
 
@@ -20,7 +21,7 @@ import torch
 
 
 def build_parser():
-    ap = argparse.ArgumentParser()
+    ap = _Parser()
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--seed", type=int, default=8888)
     ap.add_argument("--checkpoint", default="")
@@ -58,11 +59,30 @@ def build_parser():
                     help="encoder of rgb_render/%%05d.png: pillow = zlib at compress_level 4 on a pool of host threads; gpu = the "
                          "filters, one dynamic-Huffman deflate block and the Adler-32 on the GPU (lossless, the same pixels; larger "
                          "files where the image repeats at a distance), so that only the encoded bytes cross PCIe")
+    ap.add_argument("--depth-maps", dest="depth_maps", default="off", choices=["off", "u8", "u16"],
+                    help="also write <output_dir>/depth/%%05d.png per frame (the reference's inference_givenstyle_depth): off = none "
+                         "(default; the run is what it was); u8 = the reference's 8-bit values, normalised per frame over the pixels "
+                         "that hit something; u16 = 16-bit depth in world units scaled by --depth-max, comparable across frames")
+    ap.add_argument("--depth-max", dest="depth_max", type=float, default=None,
+                    help="depth that maps to 65535 with --depth-maps u16 (larger depths are clamped); required with u16")
     return ap
 
 
-def main():
-    args = build_parser().parse_args()
+class _Parser(argparse.ArgumentParser):
+    """The flags that depend on each other are checked where the arguments are parsed, so every user of build_parser() gets the
+    same errors as the command line."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.depth_maps == "u16" and ns.depth_max is None:
+            self.error("--depth-maps u16 needs --depth-max")
+        if ns.depth_max is not None and not ns.depth_max > 0:
+            self.error("--depth-max must be a positive number")
+        return ns
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     if world > 1:
@@ -114,6 +134,8 @@ def main():
         np.save(os.path.join(out, "style.npy"), np.asarray(style))    # scenedreamer.py:564
     mine = sdist.shard_frames(range(len(poses)), rank, world)
     hw = tuple(args.resolution_hw)
+    if args.depth_maps != "off":
+        return _render_with_depth(args, R, poses, mine, hw, writer, rank, world, dev)
     if args.mode == "fused":     # next frame's ray casting on a second stream beside the current frame
         frames = R.render_frames([poses[f] for f in mine], hw, args.num_samples, mode="fused")
     else:
@@ -122,6 +144,35 @@ def main():
         print(f"[rank {rank}] Rendering frame {f}", flush=True)
         writer.submit(img, f)
     writer.close()
+    _leave(world)
+
+
+def _render_with_depth(args, R, poses, mine, hw, writer, rank, world, dev):
+    """The loop of main with --depth-maps u8 | u16: every frame also yields its depth map, written to <output_dir>/depth/%05d.png
+    (the reference's directory, scenedreamer.py:720, :844) by every rank for its own frames."""
+    from . import maps as M
+    from .output import MapWriter
+    bits = 8 if args.depth_maps == "u8" else 16
+    depth_writer = MapWriter(os.path.join(args.output_dir, "depth"), bits=bits)
+    metric = M.metric_range(args.depth_max, dev) if bits == 16 else None
+    want = ("depth_u8",) if bits == 8 else ("depth",)
+    if args.mode == "fused":
+        frames = R.render_frames([poses[f] for f in mine], hw, args.num_samples, mode="fused", maps=dict.fromkeys(want))
+    else:
+        def one(f):
+            m = dict.fromkeys(want)
+            return R.render_frame(poses[f], hw, args.num_samples, mode=args.mode, maps=m), m
+        frames = (one(f) for f in mine)
+    for f, (img, m) in zip(mine, frames):
+        print(f"[rank {rank}] Rendering frame {f}", flush=True)
+        writer.submit(img, f)
+        depth_writer.submit(m["depth_u8"] if bits == 8 else M.quantise(m["depth"], metric, 16), f)
+    writer.close()
+    depth_writer.close()
+    _leave(world)
+
+
+def _leave(world):
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -263,7 +263,8 @@ def rebalance_scale(costs, scale, bands, band_ms, damping=FEEDBACK_DAMPING):
     return scale / scale.mean()
 
 
-def render_frame_tile_parallel(renderer, pose, resolution_hw, num_samples, mode="fused", group=None, balance=True, stats=None):
+def render_frame_tile_parallel(renderer, pose, resolution_hw, num_samples, mode="fused", group=None, balance=True, stats=None,
+                               maps=None):
     """Every rank renders one row band of the frame; the only exchange step of the path is the frame-wide sky mean:
     all_reduce(sum) of 64+1 numbers.  Rank 0 receives the stitched image [1,3,H,W]; the other ranks return None.
 
@@ -277,7 +278,13 @@ def render_frame_tile_parallel(renderer, pose, resolution_hw, num_samples, mode=
 
     `renderer` needs band_prepare(pose, hw, row0, row1, mode) -> {"sky_sum" f64[64], "sky_cnt" int, ...} and
     band_finish(handle, sky_avg[1,64], num_samples) -> image rows; scenedreamer_amd.renderer.Renderer provides both (and
-    row_costs)."""
+    row_costs).
+    maps: Renderer.render_frame's depth / opacity maps are not made for band-parallel frames (the frame-wide smallest and largest
+    depth would need a collective of their own): anything but None raises ValueError.  Frames sharded over ranks (shard_frames)
+    need nothing: the maps are per frame."""
+    if maps is not None:
+        raise ValueError("depth / opacity maps are not available for band-parallel frames: the frame-wide depth range would need a "
+                         "collective; render the frame on one rank (Renderer.render_frame(maps=...)) or shard whole frames")
     world = dist.get_world_size(group) if _is_init() else 1
     rank = dist.get_rank(group) if _is_init() else 0
     H, W = resolution_hw

@@ -93,6 +93,82 @@ def to_uint8_hwc(img):
     return x[0].permute(1, 2, 0).contiguous()
 
 
+class MapWriter:
+    """One-channel maps off the critical path: the reference's depth/%05d.png (scenedreamer.py:720, :844), written synchronously
+    there.  `submit(map, index)` takes a uint8 (bits = 8) or uint16 (bits = 16) [H,W] tensor -- maps.quantise's result -- copies a
+    CUDA tensor to a pinned host buffer on a side stream and hands it to `threads` workers that save '%05d.png' as Pillow mode "L" or
+    "I;16" at compress_level 4 ('%05d.npy' without Pillow, like FrameWriter); at most `depth` maps are in flight.  `close()` joins
+    the workers and re-raises what one of them raised."""
+
+    def __init__(self, output_dir, bits=8, threads=2, depth=8):
+        if bits not in (8, 16):
+            raise ValueError(f"bits must be 8 or 16, got {bits!r}")
+        self.dir, self.bits = output_dir, bits
+        os.makedirs(output_dir, exist_ok=True)
+        self.dtype = torch.uint8 if bits == 8 else torch.uint16
+        self.q = queue.Queue(maxsize=depth)
+        self.stream = None                          # made at the first CUDA map, on its device
+        self.err = None
+        self.maps_done = 0
+        self._lock = threading.Lock()
+        self.threads = [threading.Thread(target=self._run, daemon=True) for _ in range(max(1, threads))]
+        for t in self.threads:
+            t.start()
+
+    def submit(self, m, index):
+        """Enqueue map `index`; returns immediately (blocks only when `depth` maps are already in flight)."""
+        if self.err:
+            raise self.err
+        if not (isinstance(m, torch.Tensor) and m.dim() == 2 and m.dtype == self.dtype):
+            raise ValueError(f"a {self.bits}-bit map writer takes [H,W] tensors of {self.dtype}")
+        if m.is_cuda:
+            if self.stream is None:
+                self.stream = torch.cuda.Stream(m.device)
+            m = m.contiguous()
+            host = torch.empty(m.shape, dtype=m.dtype, pin_memory=True)
+            ready = torch.cuda.Event()
+            self.stream.wait_stream(torch.cuda.current_stream(m.device))
+            with torch.cuda.stream(self.stream):
+                host.copy_(m, non_blocking=True)
+                ready.record()
+            m.record_stream(self.stream)
+        else:
+            host, ready = m.contiguous(), None
+        self.q.put((index, host, ready))
+
+    def _run(self):
+        while True:
+            item = self.q.get()
+            if item is None:
+                return
+            index, host, ready = item
+            try:
+                if ready is not None:
+                    ready.synchronize()
+                arr = host.numpy()
+                if Image is not None:
+                    # (a 2-D uint8 array is mode "L"; 16 bits go in as little-endian bytes, which is what "I;16" holds)
+                    img = (Image.fromarray(arr) if self.bits == 8 else
+                           Image.frombytes("I;16", (arr.shape[1], arr.shape[0]), arr.astype("<u2").tobytes()))
+                    img.save(os.path.join(self.dir, f"{index:05d}.png"), compress_level=4)
+                else:
+                    np.save(os.path.join(self.dir, f"{index:05d}.npy"), arr)
+                with self._lock:
+                    self.maps_done += 1
+            except Exception as e:  # surfaced on the next submit()/close()
+                self.err = e
+            finally:
+                self.q.task_done()
+
+    def close(self):
+        for _ in self.threads:
+            self.q.put(None)
+        for t in self.threads:
+            t.join()
+        if self.err:
+            raise self.err
+
+
 class FrameWriter:
     def __init__(self, output_dir, fmt="png", png_compress_level=4, depth=8, video_path=None, fps=10, png_threads=3,
                  video_backend="auto", video_quality=92, video_restart_mcus=None, video_slots=2, png_backend="pillow", png_slots=2,

@@ -36,6 +36,8 @@ from .timing import _Stamps, _time_ms    # noqa: F401  (bench.py and tools/ impo
 
 MISS_COST = 0.2            # row_costs: cost of a ray that hits nothing relative to one that does (ray casting + sky MLP + CNN vs + field)
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
+MAP_OUTPUTS = ("depth", "opacity", "depth_u8", "range", "weights", "sample_depth")      # keys of render_frame's `maps`
+MAP_DEFAULT = ("depth", "opacity", "depth_u8")                                          # ... and what an empty dict stands for
 
 
 class _BoundsLiveInPrecision(types.ModuleType):
@@ -274,8 +276,10 @@ class Renderer(PrecisionState):
         depth = torch.gather(heads, 1, idx) + mid
         return depth, nd, idx
 
-    def field_unfused(self, voxel_id, depth2, raydirs, cam_ori, sky_c, sky_avg, ns, placement="torch"):
+    def field_unfused(self, voxel_id, depth2, raydirs, cam_ori, sky_c, sky_avg, ns, placement="torch", aux=None):
         """Per-ray feature net_out [R,64] from [R,M] intersections (scenedreamer.py:313-430).
+        aux: None, or a dict that receives "weights" and "depth" [R,ns] (scenedreamer.py:373-376, :346-352), the two per-sample
+        arrays of the fused kernels' aux protocol.
         placement: "torch" = sample placement by PyTorch ops on the GPU, what the unmodified reference does on the op shims
         (torch.cumsum accumulates in float32 on the GPU, in double on the CPU: the two reference paths place some samples 1 ulp
         apart, which the fine grid levels and the density head turn into net_out differences of a few 1e-4 at isolated rays);
@@ -316,6 +320,8 @@ class Renderer(PrecisionState):
         wts = (1 - torch.exp(-fe)) * torch.exp(-excl)
         sky_only = voxel_id[:, :1] == 0
         wts = wts * (~sky_only).float()
+        if aux is not None:
+            aux["weights"], aux["depth"] = wts, depth
         T = wts.sum(dim=-1, keepdim=True)
         is_gnd = (wc[:, :, 0] <= 1.0).any(dim=-1, keepdim=True)
         nosky = ((voxel_id[:, -1:] != 0) | is_gnd).float()
@@ -491,7 +497,7 @@ class Renderer(PrecisionState):
 
     # ------------------------------------------------------------------ frame
     def render_frame(self, pose, resolution_hw=(540, 960), num_samples=24, mode="unfused", cnn=True,
-                     ray_chunk=1 << 16, timers=None, cnn_mode=None, apron="minimal", _precast=None):
+                     ray_chunk=1 << 16, timers=None, cnn_mode=None, apron="minimal", _precast=None, maps=None):
         """One frame of the trajectory.  Returns image [1,3,H,W] (or net_out [1,Hp,Wp,64] if cnn=False).
 
         apron: the reference evaluates every ray of the frame padded by 15 px per side (its tile scheme,
@@ -501,7 +507,27 @@ class Renderer(PrecisionState):
         sky MLP still sees every ray of the padded frame, because its frame mean does (scenedreamer.py:592-598).  The
         image is bit-identical to "reference" (full apron) when every sample is evaluated (term_eps = 0); with early ray
         termination (the default) the 32-ray groups that stop together differ between the two windows, and the images agree
-        to the termination bound (each net_out within 2 eps = 1e-4 of the untruncated one) -- tests/test_render_gpu.py."""
+        to the termination bound (each net_out within 2 eps = 1e-4 of the untruncated one) -- tests/test_render_gpu.py.
+
+        maps: None (the call it always was: same launches, same bits), or a dict in the style of the field kernels' aux protocol --
+        its keys name what the frame should also produce, the dict receives the tensors; an empty dict = "depth", "opacity" and
+        "depth_u8" (a callable is called for the dict: render_frames' per-frame form).  What the reference's second loop writes next
+        to the image (inference_givenstyle_depth, scenedreamer.py:812-844), made by csrc/maps.hip (scenedreamer_amd/maps.py):
+          "depth" f32 [H,W]: sum over the samples of weight x sample depth (:816), cropped like the image;
+          "opacity" f32 [H,W]: sum of the weights;
+          "depth_u8" uint8 [H,W]: the pixels of the reference's depth/%05d.png (:835-844);
+          "range" int32[2]: the f32 bit patterns of the smallest / largest positive depth, (0x7F800000, 0) if nothing was hit;
+          "weights" / "sample_depth" f32 [window rays, ns]: the per-sample arrays the maps were made from, and
+          "window" (always set): (rows, cols, crop) of those arrays -- the crop is the image's, pad // 2 - apron offset.
+        The per-sample arrays come from the field launch itself: "fused" launches fused.field_render(aux={}) on the frame's window
+        (for that launch early termination is off and no 32-ray group is skipped, as the aux protocol says; colour_terms 2 has no
+        such launch and raises), "exact" fused.field_exact(aux={}), "unfused" field_unfused(aux={}) per ray chunk."""
+        if callable(maps):
+            maps = maps()
+        if maps is not None:
+            unknown = set(maps) - set(MAP_OUTPUTS) - {"window"}
+            if unknown:
+                raise ValueError(f"maps: unknown keys {sorted(unknown)}; known: {list(MAP_OUTPUTS)}")
         ev = _Stamps(timers)
         with torch.no_grad():
             ev.mark("start")
@@ -542,18 +568,28 @@ class Renderer(PrecisionState):
                 o = self.apron_offset(apron, mode, minimal=cnn or mode == "exact")
                 window = fused.Window.crop(Hp, Wp, o)
                 Hp, Wp, crop = Hp - 2 * o, Wp - 2 * o, crop - o
+            aux = {} if maps is not None else None      # (an empty dict: "weights" + "depth")
             if mode == "unfused":
-                outs = []
+                outs, auxes = [], []
                 for r0 in range(0, R, ray_chunk):
                     r1 = min(r0 + ray_chunk, R)
+                    if aux is not None:
+                        auxes.append({})
                     outs.append(self.field_unfused(vid[r0:r1], d2[:, r0:r1], rd[r0:r1], cam_ori, sky_c[r0:r1],
-                                                   sky_avg, num_samples))
+                                                   sky_avg, num_samples, **({"aux": auxes[-1]} if aux is not None else {})))
                 net_out = torch.cat(outs, dim=0)
+                if aux is not None:
+                    aux = {k: torch.cat([a[k] for a in auxes], dim=0).contiguous() for k in ("weights", "depth")}
+            elif mode == "fused" and aux is not None:
+                net_out = fused.field_render(self, vid.contiguous(), d2.contiguous(), rd.contiguous(), cam_ori, sky_c, sky_avg, num_samples,
+                                             window=window, aux=aux)
             elif mode == "fused":
                 net_out = fused.field_fused(self, vid, d2, rd, cam_ori, sky_c, sky_avg, num_samples, window=window)
             else:
-                net_out = fused.field_exact(self, vid, d2, rd, cam_ori, sky_c, sky_avg, num_samples, window=window)
+                net_out = fused.field_exact(self, vid, d2, rd, cam_ori, sky_c, sky_avg, num_samples, window=window, aux=aux)
             net_out = net_out.view(1, Hp, Wp, 64)
+            if maps is not None:
+                self._fill_maps(maps, aux["weights"], aux["depth"], Hp, Wp, crop)
             ev.mark("field")
             if not cnn:
                 ev.done()
@@ -565,6 +601,35 @@ class Renderer(PrecisionState):
             ev.done()
             return img
 
-    def render_frames(self, poses, *args, **kw):
-        """The frames of a trajectory, software-pipelined over two streams (a generator): pipeline.render_frames."""
-        return pipeline.render_frames(self, poses, *args, **kw)
+    def _fill_maps(self, maps, weights, sample_depth, rows, cols, crop):
+        """render_frame's `maps` dict from the per-sample arrays of its field launch (scenedreamer_amd/maps.py, current stream)."""
+        from . import maps as M
+        want = (set(maps) - {"window"}) or set(MAP_DEFAULT)
+        depth, opacity, rng = M.depth_maps(weights, sample_depth, rows, cols, crop, opacity="opacity" in want)
+        made = {"depth": depth, "opacity": opacity, "range": rng, "weights": weights, "sample_depth": sample_depth}
+        if "depth_u8" in want:
+            made["depth_u8"] = M.quantise(depth, rng, 8)
+        for k in want:
+            maps[k] = made[k]
+        maps["window"] = (rows, cols, crop)
+
+    def render_frames(self, poses, *args, maps=None, **kw):
+        """The frames of a trajectory, software-pipelined over two streams (a generator): pipeline.render_frames.
+        maps: None, or what every frame should produce next to its image (render_frame's `maps`): a dict whose keys are copied into a
+        fresh dict per frame, or a callable that returns that fresh dict.  The generator then yields (image, maps dict) pairs.
+        Frames rendered with maps leave the deep pipelined path: the next frame's ray casting still runs on the side stream, the
+        rest of each frame is render_frame's own sequence (the field launch with its per-sample outputs, then the map kernels)."""
+        if maps is None:
+            return pipeline.render_frames(self, poses, *args, **kw)
+        return self._frames_with_maps(poses, maps, args, kw)
+
+    def _frames_with_maps(self, poses, maps, args, kw):
+        fresh = maps if callable(maps) else (lambda: dict.fromkeys(k for k in maps if k != "window"))
+        made = []
+
+        def per_frame():
+            made.append(fresh())
+            return made[-1]
+
+        for img in pipeline.render_frames(self, poses, *args, maps=per_frame, **kw):
+            yield img, made.pop()
